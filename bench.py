@@ -16,6 +16,12 @@ inner loop: Hessian-vector products, preconditioner, CG recurrences); the iterat
 
 Run:  python bench.py [--gpus N --steps K --warmup W]
       (N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N)
+
+Such a run sets up, warms up, times the K steps and prints the result line (the headline, the solver counters and
+the in-step kernels' roofline from the events of the timed steps).  `--full` adds everything measured beside it:
+the central cost before and after, the standalone X.Q SpMM / HVP launches, the CPU baseline and its like-for-like
+replay, the boundary-regime leg and the exact leg.  `--dump-outputs DIR` writes the last timed step's iterate and
+agent status as .npy files, identical inputs from run to run, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -94,6 +100,20 @@ def super_cube_ranks(A, world):
                 sup = (ax // h) + 2 * ((ay // h) + 2 * (az // h))
                 ranks[ax + A * (ay + A * az)] = (sup * world) // 8 if A >= 2 else 0
     return ranks
+
+
+DUMP_X_BYTES = 48 << 20  # X above this size is dumped as a sample of its poses
+
+
+def dump_outputs(path, n, X, rel_change, ready):
+    """--dump-outputs: X.npy [poses, r (d + 1)] (the device layout's pose rows) with X_pose.npy, the rows' pose ids --
+    every pose, or above DUMP_X_BYTES a sorted sample drawn with a fixed seed -- and the per-agent status arrays."""
+    os.makedirs(path, exist_ok=True)
+    rows = X.reshape(n, -1)
+    keep = DUMP_X_BYTES // (8 * rows.shape[1])
+    pose = np.arange(n) if n <= keep else np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+    for name, v in (("X", rows[pose]), ("X_pose", pose), ("status_rel_change", rel_change), ("status_ready", ready)):
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(v, dtype=np.float64))
 
 
 def _free_port():
@@ -206,8 +226,22 @@ def main():
                          "exact_leg with its factor TFLOP/s, sweep roofline and the CPU port's exact-mode baseline")
     ap.add_argument("--exact-leg-k", type=int, default=48)
     ap.add_argument("--exact-leg-burnin", type=int, default=60)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beside the headline: the central cost / gradient "
+                         "norm before and after, the standalone X.Q SpMM and HVP launches, the CPU baseline with its "
+                         "like-for-like replay, the boundary-regime and exact legs (--cpu-baseline, --boundary-leg, "
+                         "--exact-leg, --certify-iters act only here), the exact preconditioner's sweep roofline and, "
+                         "N > 1, the exchange timing.  Without it: set up, warm up, time the steps, report")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one left the caller as DIR/<name>.npy (float64): "
+                         "the iterate X, one row of r (d + 1) doubles per pose (a fixed seeded sample of the poses, "
+                         "listed in X_pose.npy, above 48 MB), and every agent's status (relative change, ready flag)")
     ap.add_argument("--spawn-selftest", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if not args.full:
+        if args.certify_iters > 0:
+            ap.error("--certify-iters needs --full")
+        args.cpu_baseline = args.boundary_leg = args.exact_leg = 0
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return spawn_ranks(args.gpus)  # before torch is imported: this process never touches the GPU
@@ -375,7 +409,8 @@ def main():
         if rank == 0 and world == 1 and args.cpu_baseline and args.robust in ("L2", "GNC_TLS"):
             X_start = np.zeros(X0.size)
             eng.get_X_into(X_start)
-        f_start, gn_start = central()
+        if args.full:
+            f_start, gn_start = central()
         for _ in range(args.warmup):
             step()
         if args.pmc_calib_mb:
@@ -398,12 +433,26 @@ def main():
         ktimes = eng.kernel_times(batch_equiv=True)
         st1 = eng.stats().copy()
         b1, _ = eng.bytes()
-        f_end, gn_end = central()
-    ready, owned = eng.ready_votes()
-    if world > 1:
-        tv = torch.tensor([ready, owned], dtype=torch.int64, device="cpu" if one_device else dev)
-        dist.all_reduce(tv)
-        ready, owned = (int(v) for v in tv.cpu().numpy())
+        if args.dump_outputs:  # before any later leg moves the iterate
+            X_last = np.zeros(X0.size)
+            eng.get_X_into(X_last)
+            rel_change, ready_flag = eng.status()
+            last = [X_last, np.nan_to_num(rel_change, nan=0.0), np.maximum(ready_flag, 0).astype(np.float64)]
+            if world > 1:  # every rank holds its own agents' part, zeros elsewhere
+                for i, v in enumerate(last):
+                    tv = torch.from_numpy(v) if one_device else torch.from_numpy(v).to(dev)
+                    dist.all_reduce(tv)
+                    last[i] = tv.cpu().numpy()
+            if rank == 0:
+                dump_outputs(args.dump_outputs, g.n, *last)
+        if args.full:
+            f_end, gn_end = central()
+    if args.full:
+        ready, owned = eng.ready_votes()
+        if world > 1:
+            tv = torch.tensor([ready, owned], dtype=torch.int64, device="cpu" if one_device else dev)
+            dist.all_reduce(tv)
+            ready, owned = (int(v) for v in tv.cpu().numpy())
     if world > 1:
         tt = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if one_device else dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -472,6 +521,7 @@ def main():
         dist.all_gather_object(who, (socket.gethostname(), torch.cuda.current_device()))
         comm["ranks_per_device"] = max(who.count(w) for w in who)
         comm["devices"] = len(set(who))
+    if world > 1 and args.full:
         xt = []
         with torch.cuda.stream(stream):
             for c in range(eng.num_colors):
@@ -495,14 +545,9 @@ def main():
              "ms_max_over_ranks": float(tx[c]), "what": "pack + all_to_all (or the RCCL group) on the engine stream, "
                                                           "mean of 10, outside the timed steps"}
             for c in range(eng.num_colors)]
-    else:
+    if world == 1:
         comm["ranks_per_device"] = 1
         comm["devices"] = 1
-
-    # ---- the standalone X.Q SpMM over one colour class (the metric's "X.Q SpMM HBM GB/s")
-    fmt_bytes, spmm_ms = eng.bench_spmm(0, args.spmm_reps)
-    bsr_bytes, _ = eng.spmm_bytes(0)
-    hvp_ms = eng.bench_hvp(0, args.spmm_reps)
 
     agent_updates = num_agents * args.steps
     value = agent_updates / elapsed
@@ -559,27 +604,33 @@ def main():
                      "traffic_source": traffic["source"] if traffic else None,
                      "traffic_build_id": traffic.get("build_id") if traffic else None,
                      "traffic_note": traffic_note},
-        "xq_spmm": {"kernel": "k_spmm<5,4,MODE_XQ,edge-stream> over colour class 0 (standalone reps)",
-                    "avg_launch_ms": spmm_ms, "algorithmic_bytes_per_launch": bsr_bytes,
-                    "GBps": bsr_bytes / (spmm_ms * 1e-3) / 1e9 if spmm_ms > 0 else 0.0,
-                    "frac": bsr_bytes / (spmm_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if spmm_ms > 0 else 0.0,
-                    "format_bytes_per_launch": fmt_bytes,
-                    "traffic_bytes_per_launch": (traffic or {}).get("kernels", {}).get("XQ", {}).get(
-                        "traffic_bytes_per_launch")},
-        # guard: the X.Q-only pass does strictly less work than the HVP over the same colour, so a slower
-        # X.Q launch means the measurement (not the kernel) is off -- reported, never hidden
-        "xq_guard": {"xq_ms": spmm_ms, "hvp_ms": hvp_ms, "warning": bool(spmm_ms > hvp_ms),
-                     "note": "X.Q slower than the HVP over the same colour" if spmm_ms > hvp_ms else "ok"},
-        "hvp": {"per_s": 1e3 / hvp_ms if hvp_ms > 0 else 0.0, "avg_launch_ms": hvp_ms,
-                "agents": int(eng.agents_per_color[0]),
-                "what": "Riemannian HVP (EucHessianEta + EucHvToHv, tangent-projected) over colour class 0"},
         "tcg": tcg,
-        "central": {"f_start": f_start, "gradnorm_start": gn_start, "f_end": f_end, "gradnorm_end": gn_end,
-                    "steps_between": args.warmup + args.steps,
-                    "agents_ready_to_terminate": ready, "agents": owned, "should_terminate": ready == owned},
         "setup_s": setup_s,
         "init": init_info,
     }
+    if args.full:
+        # ---- the standalone X.Q SpMM over one colour class (the metric's "X.Q SpMM HBM GB/s")
+        fmt_bytes, spmm_ms = eng.bench_spmm(0, args.spmm_reps)
+        bsr_bytes, _ = eng.spmm_bytes(0)
+        hvp_ms = eng.bench_hvp(0, args.spmm_reps)
+        out.update({
+            "xq_spmm": {"kernel": "k_spmm<5,4,MODE_XQ,edge-stream> over colour class 0 (standalone reps)",
+                        "avg_launch_ms": spmm_ms, "algorithmic_bytes_per_launch": bsr_bytes,
+                        "GBps": bsr_bytes / (spmm_ms * 1e-3) / 1e9 if spmm_ms > 0 else 0.0,
+                        "frac": bsr_bytes / (spmm_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if spmm_ms > 0 else 0.0,
+                        "format_bytes_per_launch": fmt_bytes,
+                        "traffic_bytes_per_launch": (traffic or {}).get("kernels", {}).get("XQ", {}).get(
+                            "traffic_bytes_per_launch")},
+            # guard: the X.Q-only pass does strictly less work than the HVP over the same colour, so a slower
+            # X.Q launch means the measurement (not the kernel) is off -- reported, never hidden
+            "xq_guard": {"xq_ms": spmm_ms, "hvp_ms": hvp_ms, "warning": bool(spmm_ms > hvp_ms),
+                         "note": "X.Q slower than the HVP over the same colour" if spmm_ms > hvp_ms else "ok"},
+            "hvp": {"per_s": 1e3 / hvp_ms if hvp_ms > 0 else 0.0, "avg_launch_ms": hvp_ms,
+                    "agents": int(eng.agents_per_color[0]),
+                    "what": "Riemannian HVP (EucHessianEta + EucHvToHv, tangent-projected) over colour class 0"},
+            "central": {"f_start": f_start, "gradnorm_start": gn_start, "f_end": f_end, "gradnorm_end": gn_end,
+                        "steps_between": args.warmup + args.steps,
+                        "agents_ready_to_terminate": ready, "agents": owned, "should_terminate": ready == owned}})
     out["comm"] = comm
     if args.precon == "exact":
         # the factor of Q + 0.1 I per colour batch: tree, size, and the device numeric factorisation (it re-runs after
@@ -596,8 +647,9 @@ def main():
                     fi["factor_frac_of_mfma_f64"] = fi["factor_tflops"] / peak["mfma_f64_16x16x4_tflops"]
         # the solves' roofline: each sweep streams every stored panel once (HBM-bound; HIP events around the sweeps of
         # standalone applications over colour 0, outside the timed steps)
-        with torch.cuda.stream(stream):
-            out["exact_roofline"] = sweep_roofline(eng)
+        if args.full:
+            with torch.cuda.stream(stream):
+                out["exact_roofline"] = sweep_roofline(eng)
     out["halo"] = {"kind": args.halo if world > 1 else "none (one rank)",
                    "bytes_sent_per_step_this_rank": 8.0 * (sum(sum(v) for v in c_in) if args.halo == "color"
                                                            else eng.num_colors * int(eng.send_counts.sum())),

@@ -15,6 +15,15 @@ def load_meas(name):
                           int(z["duplicates"]))
 
 
+def golden_g2o(name, tmp_dir):
+    """Path of the dataset's g2o text, unpacked from its committed copy (golden/<name>.g2o.gz) into tmp_dir."""
+    import gzip
+    path = os.path.join(str(tmp_dir), f"{name}.g2o")
+    with gzip.open(os.path.join(GOLDEN, f"{name}.g2o.gz"), "rb") as src, open(path, "wb") as dst:
+        dst.write(src.read())
+    return path
+
+
 def random_point(r, d, n, seed):
     rng = O.SplitMix64(seed)
     M = np.array([[rng.normal() for _ in range((d + 1) * n)] for _ in range(r)])

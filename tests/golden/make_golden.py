@@ -100,7 +100,18 @@ def multirobot_exact(meas):
                         log=np.array(log, dtype=float), Xfinal=Xf)
 
 
+def g2o_copies():
+    """The reader tests' inputs: the g2o text itself, gzip-compressed (no timestamp, so the bytes are reproducible)."""
+    import gzip
+    for name in ["smallGrid3D", "sphere2500", "input_INTEL_g2o", "kitti_00", "CSAIL", "city10000"]:
+        with open(os.path.join(REF_DATA, f"{name}.g2o"), "rb") as src, \
+                open(os.path.join(HERE, f"{name}.g2o.gz"), "wb") as dst, \
+                gzip.GzipFile(filename="", mode="wb", fileobj=dst, mtime=0, compresslevel=9) as z:
+            z.write(src.read())
+
+
 def main():
+    g2o_copies()
     for name in DATASETS:
         meas = O.read_g2o(os.path.join(REF_DATA, f"{name}.g2o"))
         save_meas(name, meas)

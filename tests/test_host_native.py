@@ -9,7 +9,7 @@ import pytest
 import scipy.sparse as sp
 
 from oracle import dpgo_oracle as O
-from tests._common import GOLDEN, load_meas, rel
+from tests._common import GOLDEN, golden_g2o, load_meas, rel
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -88,10 +88,8 @@ def test_laplacian_matches_oracle(H, name):
 
 @pytest.mark.parametrize("name", ["smallGrid3D", "sphere2500", "input_INTEL_g2o", "kitti_00", "CSAIL",
                                   "city10000"])
-def test_g2o_reader_matches_oracle(H, name):
-    path = f"/root/reference/data/{name}.g2o"
-    if not os.path.exists(path):
-        pytest.skip("reference data not mounted (GPU box)")
+def test_g2o_reader_matches_oracle(H, name, tmp_path):
+    path = golden_g2o(name, tmp_path)
     g = H.Graph.read_g2o(path)
     o = O.read_g2o(path)
     a = g.arrays()

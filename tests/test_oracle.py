@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 from oracle import dpgo_oracle as O
-from tests._common import GOLDEN, load_meas, random_point, random_tangent, seeded_G, rel
+from tests._common import GOLDEN, golden_g2o, load_meas, random_point, random_tangent, seeded_G, rel
 
 
 def _triangle():
@@ -158,14 +158,11 @@ def test_multirobot_log_fixture():
     assert log[-1, 2] < log[0, 2]  # cost decreases from the chordal start
 
 
-def test_reader_fixes_on_reference_data():
+def test_reader_fixes_on_reference_data(tmp_path):
     """n = max index + 1; kitti has a blank line (no duplicate re-push)."""
-    ref = "/root/reference/data"
-    if not os.path.isdir(ref):
-        pytest.skip("reference data not mounted (GPU box)")
-    m = O.read_g2o(os.path.join(ref, "kitti_00.g2o"))
+    m = O.read_g2o(golden_g2o("kitti_00", tmp_path))
     assert m.num_poses == 4541 and m.m == 4676 and m.duplicates == 0
-    m = O.read_g2o(os.path.join(ref, "smallGrid3D.g2o"))
+    m = O.read_g2o(golden_g2o("smallGrid3D", tmp_path))
     assert m.num_poses == 125 and np.allclose(m.kappa, 12.5) and np.allclose(m.tau, 100.0)
 
 

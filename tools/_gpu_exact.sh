@@ -4,7 +4,7 @@ set -o pipefail
 TAG=${1:-r06}
 mkdir -p gpurun_out
 export TMPDIR=/tmp
-timeout -k 10 600 python3 -u bench.py --precon exact --robust GNC_TLS --burnin 60 --boundary-leg 0 --exact-leg 0 \
+timeout -k 10 600 python3 -u bench.py --full --precon exact --robust GNC_TLS --burnin 60 --boundary-leg 0 --exact-leg 0 \
   > gpurun_out/${TAG}_bench_exact_gnc.log 2>&1 || exit 1
 tail -c 400 gpurun_out/${TAG}_bench_exact_gnc.log
 timeout -k 10 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_${TAG}_exact -o run -- python3 bench.py --precon exact \

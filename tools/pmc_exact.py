@@ -24,7 +24,7 @@ def run(outdir):
         cmd = ["timeout", "-s", "KILL", "400", "rocprofv3", "--kernel-trace", "--pmc", ctr, "-d",
                os.path.join(outdir, ctr), "-o", "run", "--", sys.executable, "bench.py", "--precon", "exact",
                "--steps", "2", "--warmup", "0", "--burnin", "5", "--cpu-baseline", "0", "--boundary-leg", "0",
-               "--kernel-timing", "0", "--spmm-reps", "2", "--pmc-calib-mb", str(CALIB_MB)]
+               "--kernel-timing", "0", "--spmm-reps", "2", "--pmc-calib-mb", str(CALIB_MB), "--full"]
         with open(os.path.join(outdir, ctr + ".log"), "w") as f:
             rc = subprocess.call(cmd, stdout=f, stderr=subprocess.STDOUT, env=env)
         if rc != 0:

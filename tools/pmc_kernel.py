@@ -31,7 +31,7 @@ def run(outdir, groups):
         cmd = ["timeout", "-s", "KILL", "240", "rocprofv3", "--kernel-trace", "--pmc"] + grp.split() + [
             "-d", d, "-o", "run", "--", sys.executable, "bench.py", "--steps", "2", "--warmup", "0",
             "--cpu-baseline", "0", "--boundary-leg", "0", "--exact-leg", "0", "--kernel-timing", "0", "--spmm-reps",
-            "2"]
+            "2", "--full"]
         with open(d + ".log", "w") as f:
             rc = subprocess.call(cmd, stdout=f, stderr=subprocess.STDOUT, env=env)
         if rc != 0:

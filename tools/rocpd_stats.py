@@ -2,7 +2,8 @@
 
 --timed-steps K: only the kernels of bench.py's timed region, located in the trace as the window from
 the start of the 2K-th last tCG-start evaluation launch (k_spmm mode 5, one per colour per step) to the
-start of the first central evaluation (k_spmm mode 2) after the last one; the first timed step's
+start of the first central evaluation (k_spmm mode 2) after the last one (bench.py --full runs it; without --full
+the timed steps' kernels are the last of the trace, and the window ends there); the first timed step's
 pre-exchange kernels fall outside the window (a few microseconds)."""
 import argparse
 import glob
@@ -27,6 +28,8 @@ def main():
         t0 = ev[-n]
         t1 = c.execute(f"select min(start) from kernels where {name} like '%k_spmm<5, 4, 2,%' and start > ?",
                        (ev[-1],)).fetchone()[0]
+        if t1 is None:  # a run without --full: no central evaluation, the timed steps' kernels are the trace's last
+            t1 = c.execute("select max(end) from kernels").fetchone()[0] + 1
         where = f"where start >= {t0} and start < {t1}"
         print(f"# timed window: {(t1 - t0) / 1e6:.3f} ms over {a.timed_steps} steps "
               f"({(t1 - t0) / 1e6 / a.timed_steps:.3f} ms/step wall, kernels only below)")
