@@ -71,8 +71,31 @@ using namespace dpgo;
 
 namespace dpgo {
 
+// The one place a pose-tiled launch's tile order (LaunchCtx::order) is decided, from TUNE_TILE_ORDER.  Serpentine
+// (values >= 2): the handle remembers which way its previous pose-tiled launch walked its tiles and the next one
+// walks the other way -- HESS_M / k_tcg_updir of the merged tCG, the classic sequence's passes, retraction / F /
+// select and the engine's per-colour passes all draw from this one toggle, in launch order.
+int tile_order_next(dpgo_hip_problem h) {
+  const int v = h->tuning[dpgo::TUNE_TILE_ORDER];
+  if (v <= 0) return 0;
+  int order = dpgo::ORDER_UNIFIED;
+  if (v >= 2) {
+    if (h->tile_reverse) order |= dpgo::ORDER_REVERSE;
+    h->tile_reverse = !h->tile_reverse;
+  }
+  return order;
+}
+
 dpgo::LaunchCtx make_ctx(dpgo_hip_problem h, int flag_kind, double* partials) {
+  dpgo::LaunchCtx c = make_ctx_order(h, flag_kind, partials, 0);
+  c.order = tile_order_next(h);
+  return c;
+}
+
+// a context with a given order: launches that must share one direction (the agent groups of TUNE_SPLIT_STREAMS)
+dpgo::LaunchCtx make_ctx_order(dpgo_hip_problem h, int flag_kind, double* partials, int order) {
   dpgo::LaunchCtx c;
+  c.order = order;
   c.tile_agent = h->tile_agent.p;
   c.tile_start = h->tile_start.p;
   c.tile_count = h->tile_count.p;
@@ -1445,6 +1468,7 @@ int dpgo_hip_problem_create_batch(int num_agents, const int* poses_per_agent, in
       hipStreamSynchronize(nullptr) != hipSuccess)
     return cleanup(fail(DPGO_HIP_EDEVICE, "device upload failed"));
   if (const char* ev = std::getenv("DPGO_FUSE_FINALIZE")) h->fuse_finalize = std::atoi(ev);
+  if (const char* ev = std::getenv("DPGO_TILE_ORDER")) h->tuning[dpgo::TUNE_TILE_ORDER] = std::atoi(ev);
   if (hipHostMalloc(reinterpret_cast<void**>(&h->pub_host), sizeof(int) * num_agents,
                     hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
       hipHostGetDevicePointer(reinterpret_cast<void**>(&h->pub_dev), h->pub_host, 0) != hipSuccess)
@@ -1830,6 +1854,17 @@ int dpgo_hip_get_trace(dpgo_hip_problem h, int agent, double* out, int max_recor
 #endif
 const char* dpgo_hip_build_id(void) { return DPGO_SOURCE_HASH; }
 
+int dpgo_hip_tile_of_block(int block, int num_blocks, int reverse) {
+  if (num_blocks < 1 || block < 0 || block >= num_blocks) return -1;
+  return dpgo::tile_of_block(block, num_blocks, reverse);
+}
+
+int dpgo_hip_tile_map(int num_blocks, int reverse, int* tiles) {
+  if (num_blocks < 1 || !tiles) return fail(DPGO_HIP_EINVAL, "tile map needs >= 1 block and an output array");
+  for (int b = 0; b < num_blocks; ++b) tiles[b] = dpgo::tile_of_block(b, num_blocks, reverse);
+  return DPGO_HIP_OK;
+}
+
 int dpgo_hip_optimize_dev(dpgo_hip_problem h, const dpgo_opt_params* params, const double* X_in,
                           double* X_out, const int* agent_enabled_host, dpgo_opt_result* results) {
   return dpgo::optimize_dev_status(h, params, X_in, X_out, agent_enabled_host, results, nullptr);
@@ -2108,11 +2143,14 @@ int dpgo::optimize_dev_status(dpgo_hip_problem h, const dpgo_opt_params* params,
     // finalize rows of that agent range; every kernel of the iteration reads and writes only those agents'
     // poses (Q and the tCG vectors are block-diagonal over agents), so the halves are independent and each
     // agent's arithmetic is the unsplit launch's, bit for bit.
-    auto launch_merged_range = [&](int j, int mode, int flag, int op, int a0, int a1, hipStream_t on) -> int {
+    // order_h / order_u: the tile orders of the iteration's HESS_M and k_tcg_updir, drawn once per iteration so that
+    // every agent group runs a phase in the same direction (each group's own tiles then alternate launch by launch)
+    auto launch_merged_range = [&](int j, int mode, int flag, int op, int a0, int a1, hipStream_t on, int order_h,
+                                   int order_u) -> int {
       const int t0 = h->h_agent_tile_off[a0], t1 = h->h_agent_tile_off[a1];
       if (t1 == t0) return DPGO_HIP_OK;
-      auto sub = [&](double* partials) {
-        dpgo::LaunchCtx c = make_ctx(h, flag, partials + static_cast<long>(t0) * dpgo::kPartialStride);
+      auto sub = [&](double* partials, int order) {
+        dpgo::LaunchCtx c = dpgo::make_ctx_order(h, flag, partials + static_cast<long>(t0) * dpgo::kPartialStride, order);
         c.tile_agent += t0;
         c.tile_start += t0;
         c.tile_count += t0;
@@ -2137,9 +2175,9 @@ int dpgo::optimize_dev_status(dpgo_hip_problem h, const dpgo_opt_params* params,
       fin.state += a0;
       fin.out_sums += 4 * a0;
       if (fin.trace) fin.trace += static_cast<long>(a0) * fin.trace_cap * dpgo::kTraceWidth;
-      DPGO_TRY(dpgo::spmm_launch(h, mode, sub(h->pa.p), sa));
+      DPGO_TRY(dpgo::spmm_launch(h, mode, sub(h->pa.p, order_h), sa));
       HIP_TRY(dpgo::launch_finalize(fin, a1 - a0, on));
-      auto cu = sub(h->peh.p);
+      auto cu = sub(h->peh.p, order_u);
       cu.flag_kind = dpgo::FLAG_TCG_MODE;
       HIP_TRY(dpgo::launch_tcg_updir(r, b, cu, x1, h->minv.p, pmode, h->delta.p, h->Hdelta.p, h->eta.p,
                                      j == 0 ? h->g.p : h->rv.p, h->rv.p, j == 0 ? 1 : 0,
@@ -2181,13 +2219,15 @@ int dpgo::optimize_dev_status(dpgo_hip_problem h, const dpgo_opt_params* params,
       }
       for (int j = 0; j < P.tr_max_inner; ++j) {
         const int mode = j == 0 ? dpgo::MODE_HESS_QF_M : dpgo::MODE_HESS_M;
-        DPGO_TRY(launch_merged_range(j, mode, dpgo::FLAG_TCG, dpgo::OP_TCG_STEP_CHECK, first(0), first(1), on(0)));
+        const int oh = dpgo::tile_order_next(h), ou = dpgo::tile_order_next(h);
+        DPGO_TRY(launch_merged_range(j, mode, dpgo::FLAG_TCG, dpgo::OP_TCG_STEP_CHECK, first(0), first(1), on(0), oh, ou));
         if (offset && j == 0) {
           HIP_TRY(hipEventRecord(h->split_fork, h->stream));
           HIP_TRY(hipStreamWaitEvent(on(1), h->split_fork, 0));
         }
         for (int g = 1; g < G; ++g)
-          DPGO_TRY(launch_merged_range(j, mode, dpgo::FLAG_TCG, dpgo::OP_TCG_STEP_CHECK, first(g), first(g + 1), on(g)));
+          DPGO_TRY(launch_merged_range(j, mode, dpgo::FLAG_TCG, dpgo::OP_TCG_STEP_CHECK, first(g), first(g + 1), on(g), oh,
+                                       ou));
       }
       for (int g = 1; g < G; ++g) {
         HIP_TRY(hipEventRecord(h->split_join[g - 1], on(g)));

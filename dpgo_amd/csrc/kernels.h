@@ -69,6 +69,23 @@ enum TraceField {
   TR_ACCEPTED = 13, TR_NGF = 14, TR_RUN = 15
 };
 
+// Block -> tile map of every pose-tiled launch.  Blocks b and b + 8 share an XCD (cdna_hip_programming.md 5.5 T1), so
+// XCD slot x = b & 7 owns one contiguous range of tiles (q + 1 tiles for the slots below nwg & 7, q = nwg >> 3 for
+// the others) and its i-th block (i = b >> 3) takes the range's i-th tile: neighbouring tiles share that XCD's L2.
+// reverse != 0 walks every range from its end (rank cnt_x - 1 - i): a block stays on its XCD's range, so a launch
+// that runs opposite to the previous one starts on the tiles that one touched last, while their lines are still in
+// the on-die caches.  A bijection on [0, nwg) for every nwg >= 1.  Speed only -- placement never affects results.
+__host__ __device__ __forceinline__ int tile_of_block(int b, int nwg, int reverse) {
+  const int xcd = b & 7, q = nwg >> 3, r = nwg & 7, i = b >> 3;
+  const int first = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
+  const int cnt = xcd < r ? q + 1 : q;
+  return first + (reverse ? cnt - 1 - i : i);
+}
+// LaunchCtx::order bits (the host's tile_order_next decides them from TUNE_TILE_ORDER; 0 = the maps before the
+// unified one: the edge-stream SpMM remapped forward, every other pass tile = block)
+enum TileOrder { ORDER_UNIFIED = 1,    // every pose-tiled kernel takes its tile from tile_of_block
+                 ORDER_REVERSE = 2 };  // ... walking the XCD ranges from their ends
+
 // Tile set + per-agent state for one launch.
 struct LaunchCtx {
   const int* tile_agent;  // [num_tiles]
@@ -84,6 +101,7 @@ struct LaunchCtx {
   // launch issues the tile's stage loads right after the tile's scalar header instead of after a round trip
   // through its poses' incidence pointers
   const int4* tile_meta;
+  int order = 0;          // TileOrder bits: which tile each block takes (pose-tiled kernels only)
 };
 
 enum QFormat { QFMT_BSR = 0, QFMT_EDGES = 1 };
@@ -342,7 +360,13 @@ enum TuneKey { TUNE_SPMM_VARIANT = 0, TUNE_EDGE_VARIANT = 1, TUNE_EPI_PREFETCH =
                                    //    4: 3 + one edge-loop pipeline per pose in the merged modes (bit 8);
                                    //    5: rotated + one pipeline in every mode; 6 (default since round 5): 5 but the
                                    //    half passes (F, QF) plain; 0: the round-3 kernels
-               TUNE_COUNT = 13 };
+               TUNE_TILE_ORDER = 13,  // block -> tile map of the pose-tiled launches (DPGO_TILE_ORDER overrides): 0 the
+                                      // SpMM remapped per XCD, vector passes tile = block; 1 every pass by
+                                      // tile_of_block, forward; 2 serpentine (each launch over a handle's tiles
+                                      // opposite to the previous one); 3 was 2 + non-temporal loads / stores on the
+                                      // one-use streams: measured slower than 2 and taken out of the kernels
+                                      // (DESIGN.md 3.6), so 3 now runs as 2
+               TUNE_COUNT = 14 };
 // dd_mask of the merged tCG partials for the kernel a handle with these tuning keys and Q format runs
 inline int merged_dd_mask(int fmt, const int* tuning) {
   return fmt == QFMT_EDGES && tuning[TUNE_SPMM_V2] > 0 ? kMergedDdSlots : kMergedDdSlotsV1;

@@ -294,12 +294,14 @@ struct PoseLane {
   int kk;  // column this lane owns (k < B) else -1
 };
 
-// XCD-aware bijective remap (cdna_hip_programming.md 5.5 T1): blocks b and b+8 share an XCD, so
-// give XCD slot x a contiguous range of tiles; neighbouring tiles then share that XCD's L2 for
-// the gathered X rows.  Speed only -- placement never affects results.
-__device__ __forceinline__ int xcd_remap(int b, int nwg) {
-  const int xcd = b & 7, q = nwg >> 3, r = nwg & 7;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
+// The tile this block works on (tile_of_block, kernels.h; grid = the launch's tiles).  XCD: the kernel was remapped
+// before the unified map (the edge-stream SpMM), so it follows tile_of_block whatever LaunchCtx::order says; the
+// others only with ORDER_UNIFIED (order 0: tile = block).  Block-uniform scalar arithmetic.
+template <bool XCD = false>
+__device__ __forceinline__ int launch_tile(const LaunchCtx& c) {
+  const int b = static_cast<int>(blockIdx.x);
+  if (!XCD && (c.order & ORDER_UNIFIED) == 0) return b;
+  return tile_of_block(b, static_cast<int>(gridDim.x), c.order & ORDER_REVERSE);
 }
 
 template <int B, bool XCD = false>
@@ -308,7 +310,7 @@ __device__ __forceinline__ PoseLane pose_lane(const LaunchCtx& c) {
   p.lane = threadIdx.x & 63;
   p.wave = threadIdx.x >> 6;
   p.k = p.lane & 3;
-  p.tile = XCD ? xcd_remap(static_cast<int>(blockIdx.x), static_cast<int>(gridDim.x)) : static_cast<int>(blockIdx.x);
+  p.tile = launch_tile<XCD>(c);
   p.agent = c.tile_agent[p.tile];
   p.pslot = p.wave * kPosesPerWave + (p.lane >> 2);
   p.ok = p.pslot < c.tile_count[p.tile];
@@ -2446,7 +2448,7 @@ __global__ __launch_bounds__(64) void k_polar_comb(LaunchCtx c, const double* __
   constexpr int PW = R * B;
   constexpr int PS = PW + 1;
   __shared__ double sm[64 * PS];
-  const int tile = blockIdx.x;
+  const int tile = launch_tile(c);
   const int agent = c.tile_agent[tile];
   if (tile_skipped(c, agent)) return;
   const int count = c.tile_count[tile];
@@ -2554,7 +2556,7 @@ __global__ __launch_bounds__(64) void k_polar_vnext(LaunchCtx c, const double* _
   constexpr int PW = R * B;
   constexpr int PS = PW + 1;
   __shared__ double sm[64 * PS];
-  const int tile = blockIdx.x;
+  const int tile = launch_tile(c);
   const int agent = c.tile_agent[tile];
   if (tile_skipped(c, agent)) return;
   const int count = c.tile_count[tile];
@@ -4546,7 +4548,7 @@ template <int MODE>
 hipError_t spmm_mode(int r, int b, dim3 grid, const LaunchCtx& c, const QView& q, const SpmmArgs& a);
 
 #ifndef DPGO_SPMM_TU
-int g_tuning[TUNE_COUNT] = {0, -1, 1, 0, 0, 0, 0, 0, 0, 0, 1, 6, 1};
+int g_tuning[TUNE_COUNT] = {0, -1, 1, 0, 0, 0, 0, 0, 0, 0, 1, 6, 1, 2};
 
 bool supported_rb(int r, int b) {
   if (b == 3) return r >= 2 && r <= 8;

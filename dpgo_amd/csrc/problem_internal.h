@@ -204,6 +204,9 @@ struct dpgo_hip_problem_s {
   // finalize after an SpMM: 0 separate k_finalize launch, 1 / 2 fused into the SpMM's last block per
   // agent (SpmmArgs::fin_mode); DPGO_FUSE_FINALIZE overrides
   int fuse_finalize = 0;
+  // serpentine tile order (TUNE_TILE_ORDER >= 2): the handle's next pose-tiled launch walks its tiles in reverse
+  // (tile_order_next flips it at every such launch)
+  bool tile_reverse = false;
   // host-mapped status words written by k_finalize (zero-copy polling, no stream sync)
   int* pub_host = nullptr;
   int* pub_dev = nullptr;
@@ -250,7 +253,10 @@ struct dpgo_hip_problem_s {
 
 namespace dpgo {
 // helpers implemented in capi.cpp
+// the launch context of the handle's next pose-tiled launch: its tile order comes from tile_order_next
 LaunchCtx make_ctx(dpgo_hip_problem h, int flag_kind, double* partials);
+LaunchCtx make_ctx_order(dpgo_hip_problem h, int flag_kind, double* partials, int order);
+int tile_order_next(dpgo_hip_problem h);
 int problem_ready(dpgo_hip_problem h);
 int ensure_work_public(dpgo_hip_problem h);
 

@@ -106,6 +106,8 @@ _SIGS = [
     ("dpgo_hip_set_trace", [C.c_void_p, C.c_int], C.c_int),
     ("dpgo_hip_get_trace", [C.c_void_p, C.c_int, _dp, C.c_int, _ip], C.c_int),
     ("dpgo_hip_build_id", [], C.c_char_p),
+    ("dpgo_hip_tile_of_block", [C.c_int, C.c_int, C.c_int], C.c_int),
+    ("dpgo_hip_tile_map", [C.c_int, C.c_int, _ip], C.c_int),
 ]
 STATS_INTS = 13
 STATS_FIELDS = ["calls", "early", "runs", "tcg_iters", "NEGCURVTURE", "EXCREGION", "LCON", "SCON", "MAXITER",
@@ -166,6 +168,18 @@ def device_count() -> int:
 def build_id() -> str:
     """Source hash compiled into the loaded libdpgo_hip.so (__graft_entry__.source_hash())."""
     return lib().dpgo_hip_build_id().decode()
+
+
+def tile_of_block(block: int, num_blocks: int, reverse: int) -> int:
+    """The tile a block of a pose-tiled launch works on (dpgo_hip_tile_of_block)."""
+    return int(lib().dpgo_hip_tile_of_block(int(block), int(num_blocks), int(reverse)))
+
+
+def tile_map(num_blocks: int, reverse: int) -> np.ndarray:
+    """tile_of_block of every block of a launch (dpgo_hip_tile_map)."""
+    out = np.empty(int(num_blocks), np.int32)
+    _check(lib().dpgo_hip_tile_map(int(num_blocks), int(reverse), out.ctypes.data_as(_ip)))
+    return out
 
 
 def rccl_unique_id() -> bytes:

@@ -213,6 +213,14 @@ int dpgo_hip_get_trace(dpgo_hip_problem h, int agent, double* out, int max_recor
  * without it): lets a caller check that a shipped binary matches the tree it runs with. */
 const char* dpgo_hip_build_id(void);
 
+/* The tile that block `block` of a pose-tiled launch of `num_blocks` blocks works on (the kernels' own map, tuning
+ * key 13): blocks b and b + 8 share an XCD, XCD slot b & 7 owns one contiguous range of tiles and walks it from its
+ * start, or from its end when reverse != 0.  A bijection on [0, num_blocks); -1 for a block outside it.  No device
+ * is needed. */
+int dpgo_hip_tile_of_block(int block, int num_blocks, int reverse);
+/* The same for every block of the launch: tiles[b], b < num_blocks. */
+int dpgo_hip_tile_map(int num_blocks, int reverse, int* tiles);
+
 /* ---- certification (not in the reference: parity is pinned against a sparse
  * eigensolver on the explicitly formed matrix) --------------------------------------------------
  * Smallest eigenvalue of the certificate matrix S(X) = Q - Lambda(X), Lambda = blockdiag of
