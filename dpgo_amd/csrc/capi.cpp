@@ -2087,6 +2087,13 @@ int dpgo::optimize_dev_status(dpgo_hip_problem h, const dpgo_opt_params* params,
     // iteration instead of five, no z vector.  The exact preconditioner and TUNE_FUSE_TCG keep the
     // classic sequence (TUNE_CLASSIC_TCG forces it).
     const bool merged = qf0 && !fuse_tcg && h->tuning[dpgo::TUNE_CLASSIC_TCG] == 0;
+    // TUNE_TAIL_FUSE: the last iteration's k_tcg_updir (eta += step delta and the <eta_old, Hdelta> partial, nothing
+    // else) is not launched; the retraction that follows applies the step from registers (RetractTail).  Every path
+    // to the last iteration goes through launch_merged / launch_merged_range, which set tail_pending instead of
+    // launching; launch_candidate hands it to the retraction.  Both kernels would read the state the last
+    // OP_TCG_STEP_CHECK / OP_TCG_CHECK_M left: no finalize runs between them.
+    const bool tail_fuse = merged && h->tuning[dpgo::TUNE_TAIL_FUSE] > 0;
+    bool tail_pending = false;  // this Run's last merged iteration was queued without its k_tcg_updir
     auto launch_merged = [&](int j, int mode, int flag, int op, bool publish = true) -> int {
       auto ch = make_ctx(h, flag, h->pa.p);
       const int tag = publish ? next_tag(h) : 0;
@@ -2105,6 +2112,10 @@ int dpgo::optimize_dev_status(dpgo_hip_problem h, const dpgo_opt_params* params,
       fin.dd_mask = dpgo::merged_dd_mask(h->fmt, h->tuning);  // which merged partials are double-double
       fin.rz_pc = rz_pc ? 1 : 0;
       DPGO_TRY(spmm_then_finalize(h, mode, ch, sa, fin));
+      if (tail_fuse && j + 1 == P.tr_max_inner) {  // the retraction draws the tile order this launch would have
+        tail_pending = true;
+        return DPGO_HIP_OK;
+      }
       auto cu = make_ctx(h, dpgo::FLAG_TCG_MODE, h->peh.p);
       HIP_TRY(dpgo::launch_tcg_updir(r, b, cu, x1, h->minv.p, pmode, h->delta.p, h->Hdelta.p, h->eta.p,
                                      j == 0 ? h->g.p : h->rv.p, h->rv.p, j == 0 ? 1 : 0,
@@ -2113,12 +2124,17 @@ int dpgo::optimize_dev_status(dpgo_hip_problem h, const dpgo_opt_params* params,
     };
     auto launch_candidate = [&](int run_flag, int filter) -> int {
       auto cr = make_ctx(h, run_flag, h->pa.p);
+      // a pending last step: its partial goes to peh (the rho test's FinalizeArgs::pc below), the retraction's to pa
+      const dpgo::RetractTail tail{h->delta.p, h->Hdelta.p, h->peh.p, P.tr_max_inner == 1 ? 1 : 0};
+      const bool with_tail = tail_pending && run_flag != dpgo::FLAG_RUN_IMPL;
       HIP_TRY(dpgo::launch_retract(r, b, cr, x1, h->eta.p, 1.0, x2, h->g.p, nullptr, h->delta.p,
-                                   status_fold ? st->ref : nullptr));
+                                   status_fold ? st->ref : nullptr, with_tail ? &tail : nullptr));
+      if (with_tail) tail_pending = false;
       // single Run: only f(x2) and |grad(x2)| are consumed (fOpt / gradNormOpt), |grad(x2)| only as a
       // statistic
       const int rtag = next_tag(h);
       dpgo::OptScalars orho = o;
+      orho.tail_fused = with_tail ? 1 : 0;
       if (status_fold) {
         orho.status_fold = 1;
         orho.rel_tol = st->rel_tol;
@@ -2177,6 +2193,10 @@ int dpgo::optimize_dev_status(dpgo_hip_problem h, const dpgo_opt_params* params,
       if (fin.trace) fin.trace += static_cast<long>(a0) * fin.trace_cap * dpgo::kTraceWidth;
       DPGO_TRY(dpgo::spmm_launch(h, mode, sub(h->pa.p, order_h), sa));
       HIP_TRY(dpgo::launch_finalize(fin, a1 - a0, on));
+      if (tail_fuse && j + 1 == P.tr_max_inner) {  // every group's last step waits for the (unsplit) retraction
+        tail_pending = true;
+        return DPGO_HIP_OK;
+      }
       auto cu = sub(h->peh.p, order_u);
       cu.flag_kind = dpgo::FLAG_TCG_MODE;
       HIP_TRY(dpgo::launch_tcg_updir(r, b, cu, x1, h->minv.p, pmode, h->delta.p, h->Hdelta.p, h->eta.p,
@@ -2219,7 +2239,9 @@ int dpgo::optimize_dev_status(dpgo_hip_problem h, const dpgo_opt_params* params,
       }
       for (int j = 0; j < P.tr_max_inner; ++j) {
         const int mode = j == 0 ? dpgo::MODE_HESS_QF_M : dpgo::MODE_HESS_M;
-        const int oh = dpgo::tile_order_next(h), ou = dpgo::tile_order_next(h);
+        // (a fused last iteration launches no k_tcg_updir and draws no order for it)
+        const int oh = dpgo::tile_order_next(h);
+        const int ou = tail_fuse && j + 1 == P.tr_max_inner ? 0 : dpgo::tile_order_next(h);
         DPGO_TRY(launch_merged_range(j, mode, dpgo::FLAG_TCG, dpgo::OP_TCG_STEP_CHECK, first(0), first(1), on(0), oh, ou));
         if (offset && j == 0) {
           HIP_TRY(hipEventRecord(h->split_fork, h->stream));

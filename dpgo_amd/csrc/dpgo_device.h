@@ -44,6 +44,8 @@ struct AgentState {
   int r_stop_lcon;   // the threshold's kind: kappa < |r_0|^theta (LCON) or not (SCON)
   int eh_pending;    // merged tCG: a k_tcg_updir left <eta_old, Hdelta> partials (FinalizeArgs::pc) that the
                      // next OP_TCG_STEP_CHECK / OP_RHO folds into eta_Heta with step and d_Hd
+  int st_tail;       // cumulative, beside the statistics below (not part of dpgo_hip_stats): Runs whose last tCG
+                     // step the retraction applied (TUNE_TAIL_FUSE; the byte model's count of the fused passes)
   double status_rel_change;  // PGOAgentStatus::relativeChange = |X - XPrev| / sqrt(n) (OP_STATUS)
   // cumulative statistics since the handle was created (never reset; read by dpgo_hip_stats)
   int st_calls;      // optimize calls in which the agent was enabled

@@ -146,6 +146,7 @@ struct OptScalars {
   int first_full;  // OP_TCG_STEP of a first step measured by MODE_HESS_QF (statistics only)
   int status_fold;  // OP_RHO of a single Run also sets the PGOAgent status of the agents it decides from
                     // k_retract's |x2 - ref|^2 / |x1 - ref|^2 partials (pa slots 2, 3)
+  int tail_fused;   // OP_RHO after a retraction that applied the pending last tCG steps (statistics only)
 };
 
 struct FinalizeArgs {
@@ -366,7 +367,12 @@ enum TuneKey { TUNE_SPMM_VARIANT = 0, TUNE_EDGE_VARIANT = 1, TUNE_EPI_PREFETCH =
                                       // opposite to the previous one); 3 was 2 + non-temporal loads / stores on the
                                       // one-use streams: measured slower than 2 and taken out of the kernels
                                       // (DESIGN.md 3.6), so 3 now runs as 2
-               TUNE_COUNT = 14 };
+               TUNE_TAIL_FUSE = 14,  // merged tCG: 1 the last iteration's k_tcg_updir is not launched, the retraction
+                                     // applies its step from registers (RetractTail); 0 both launches
+               TUNE_NEXT_Y = 15,  // engine: 1 the non-selected pass over the colour selected next also writes that
+                                  // colour's next updateY and status XPrev (PolarNext), and the selected colour's
+                                  // own pass is skipped when the prediction held; 0 both passes
+               TUNE_COUNT = 16 };
 // dd_mask of the merged tCG partials for the kernel a handle with these tuning keys and Q format runs
 inline int merged_dd_mask(int fmt, const int* tuning) {
   return fmt == QFMT_EDGES && tuning[TUNE_SPMM_V2] > 0 ? kMergedDdSlots : kMergedDdSlotsV1;
@@ -407,18 +413,37 @@ hipError_t launch_tcg_updir(int r, int b, const LaunchCtx& c, const double* X, c
                             int first, int last);
 // status_ref (optional, with g): also the partials |out - ref|^2 and |X - ref|^2 (slots 2, 3) for the status
 // folded into the rho test (OptScalars::status_fold)
+// tail (optional; needs c.state): the merged tCG's last step, not yet applied (no k_tcg_updir ran for it).  Agents
+// with a step pending take eta = fma(step, delta, eta_old) with eta_old read from V (zero when first), leave
+// <eta_old, Hdelta> in peh (k_tcg_updir's partial layout; a second destination beside c.partials) and do not
+// store eta; every other agent is retracted as without it.
+struct RetractTail {
+  const double* delta;
+  const double* Hdelta;
+  double* peh;
+  int first;
+};
 hipError_t launch_retract(int r, int b, const LaunchCtx& c, const double* X, const double* V, double scale,
                           double* out, const double* g, const double* HV, const double* delta_impl = nullptr,
-                          const double* status_ref = nullptr);
+                          const double* status_ref = nullptr, const RetractTail* tail = nullptr);
 hipError_t launch_tangent(int r, int b, const LaunchCtx& c, const double* X, const double* V, double* out);
 hipError_t launch_precond(int r, int b, const LaunchCtx& c, const double* X, const double* Minv, int pmode,
                           const double* V, double* out);
+// next (optional): two more outputs of the same pass, y = project(sa out + sb V) (V as this pass leaves it) and,
+// when given, xprev = out -- the combination pass a later launch would run on this one's outputs
+struct PolarNext {
+  double sa, sb;
+  double* y;
+  double* xprev;
+};
 // xcopy (optional): the X operand as read (PGOAgent::iterate's XPrev = X, src/PGOAgent.cpp:673)
 hipError_t launch_polar_vnext(int r, int b, const LaunchCtx& c, const double* X, double* V, const double* Yv,
-                              double gv, double sa, double sb, double* out, double* xcopy = nullptr);
+                              double gv, double sa, double sb, double* out, double* xcopy = nullptr,
+                              const PolarNext* next = nullptr);
 hipError_t launch_polar_comb(int r, int b, const LaunchCtx& c, const double* A, const double* Bv,
                              const double* ca, const double* cb, double* out, const double* Cv = nullptr,
-                             double sa = 1.0, double sb = 0.0, double* out2 = nullptr, double* xcopy = nullptr);
+                             double sa = 1.0, double sb = 0.0, double* out2 = nullptr, double* xcopy = nullptr,
+                             const PolarNext* next = nullptr);
 // PGOAgent::computeConvergedLoopClosureRatio (src/PGOAgent.cpp:1247-1289): per agent a, the share of
 // its loop closures idx[off[a] .. off[a+1]) whose weight w[] is exactly 1 or 0 (0/0 = NaN, as there)
 hipError_t launch_conv_ratio(int num_agents, const int* off, const int* idx, const double* w, double* ratio,

@@ -1279,6 +1279,7 @@ __device__ __forceinline__ void finalize_scalar(const FinalizeArgs& f, int agent
       break;
     }
     case OP_RHO: {  // pa: <g,eta> [, <eta,HV>, |x2 - ref|^2, |x1 - ref|^2]; pb: f(x2), |grad(x2)|^2
+      if (o.tail_fused && s.eh_pending && f.nq_c >= 1) s.st_tail += 1;  // the step k_retract applied
       fold_eta_heta(f, tot, s);
       if (!s.run_active) break;
       const bool sfold = o.status_fold && f.nq_a == 4;  // pa carries the status partials (slots 2, 3)
@@ -2319,14 +2320,19 @@ __global__ __launch_bounds__(kThreads) void k_tcg_updir(LaunchCtx c, const doubl
 // (the tCG carries <eta, Heta> as a scalar and passes none).  For agents whose eta is implicit
 // (AgentState::eta_implicit) and delta_impl is given, eta = step delta is formed here (the same fma the
 // update kernel would have stored) and the dots come from OP_TCG_STEP instead.
-template <int R, int B>
+// TAIL (merged tCG, TUNE_TAIL_FUSE): the last tCG iteration's k_tcg_updir is not launched and its step is applied
+// here, for the agents it would have visited (a step pending: tcg_mode != 2 and eta not implicit, the state after
+// the same finalize): V holds eta_old, eta = fma(step, delta, eta_old) stays in registers and is not stored, and
+// the <eta_old, Hdelta> partial goes to tail.peh in k_tcg_updir's layout -- the same fma sequences on the same
+// operands.  Agents that stopped earlier read their final eta from V as before and leave tail.peh alone.
+template <int R, int B, bool TAIL>
 __global__ __launch_bounds__(kThreads) void k_retract(LaunchCtx c, const double* __restrict__ X,
                                                       const double* __restrict__ V, double scale,
                                                       double* __restrict__ out,
                                                       const double* __restrict__ g,
                                                       const double* __restrict__ HV,
                                                       const double* __restrict__ delta_impl,
-                                                      const double* __restrict__ status_ref) {
+                                                      const double* __restrict__ status_ref, RetractTail tail) {
   constexpr int D = B - 1;
   const PoseLane p = pose_lane<B>(c);
   if (tile_skipped(c, p.agent)) return;
@@ -2335,7 +2341,27 @@ __global__ __launch_bounds__(kThreads) void k_retract(LaunchCtx c, const double*
   const bool impl = delta_impl != nullptr && c.state != nullptr && c.state[p.agent].eta_implicit;
   double xcol[R], vcol[R];
   load_col<R, B>(X, p.j, p.k, p.ok, xcol);
-  if (impl) {
+  bool pend = false;  // uniform per tile
+  if constexpr (TAIL) pend = c.state[p.agent].tcg_mode != 2 && !c.state[p.agent].eta_implicit;
+  if (TAIL && pend) {
+    const double step = c.state[p.agent].step;
+    double dcol[R], hcol[R];
+    load_col<R, B>(tail.delta, p.j, p.k, p.ok, dcol);
+    load_col<R, B>(tail.Hdelta, p.j, p.k, p.ok, hcol);
+    if (tail.first) {  // eta = 0 at the start of tCG
+#pragma unroll
+      for (int a = 0; a < R; ++a) vcol[a] = 0.0;
+    } else {
+      load_col<R, B>(V, p.j, p.k, p.ok, vcol);
+    }
+    double eh = 0.0;  // <eta_old, Hdelta>
+#pragma unroll
+    for (int a = 0; a < R; ++a) eh = fma(vcol[a], hcol[a], eh);
+#pragma unroll
+    for (int a = 0; a < R; ++a) vcol[a] = fma(step, dcol[a], vcol[a]);
+    dd rz[2] = {{0.0, 0.0}, {0.0, 0.0}};  // no next iteration: as k_tcg_updir's last
+    block_partials_dd<2>(own ? eh : 0.0, rz, tail.peh, p.tile);
+  } else if (impl) {
     const double step = c.state[p.agent].step;
     load_col<R, B>(delta_impl, p.j, p.k, p.ok, vcol);
 #pragma unroll
@@ -2429,13 +2455,19 @@ __global__ __launch_bounds__(kThreads) void k_precond(LaunchCtx c, const double*
   store_vec<R>(out, off, own, oc);
 }
 
+// a0 A + b0 B as one rounded product and one fma, in this order: the fused passes (NEXT below and in k_polar_vnext)
+// form a later launch's combination ahead of time and must round as that launch does
+__device__ __forceinline__ double comb_xv(double a0, double av, double b0, double bv) { return fma(b0, bv, a0 * av); }
+
 // out = LiftedSEManifold::project(ca A + cb B) (or A + cb (B - C)) with per-agent (or scalar)
 // coefficients.  A tile's 64 poses are one contiguous span of 64 r b doubles: the combination is
 // elementwise, so it is formed while the span streams through LDS with fully coalesced loads; then
 // thread t polar-projects pose t from LDS (row stride r b + 1 doubles: conflict-free b64 reads) and
 // the span streams back out coalesced (optionally to a second destination).
 // (src/manifold/LiftedSEManifold.cpp:34-45; Nesterov updateY/updateV src/PGOAgent.cpp:1075-1091)
-template <int R, int B>
+// NEXT (TUNE_NEXT_Y; the a0 A + b0 B form only): two more outputs of the same pass, ynext = project(sa2 out + sb2 B)
+// and xprev = out -- what a second launch with A = out and xcopy = xprev would compute, by the same comb_xv.
+template <int R, int B, bool NEXT>
 __global__ __launch_bounds__(64) void k_polar_comb(LaunchCtx c, const double* __restrict__ A,
                                                    const double* __restrict__ Bv,
                                                    const double* __restrict__ ca,
@@ -2443,7 +2475,8 @@ __global__ __launch_bounds__(64) void k_polar_comb(LaunchCtx c, const double* __
                                                    double* __restrict__ out,
                                                    const double* __restrict__ Cv, double sa,
                                                    double sb, double* __restrict__ out2,
-                                                   double* __restrict__ xcopy) {
+                                                   double* __restrict__ xcopy, double sa2, double sb2,
+                                                   double* __restrict__ ynext, double* __restrict__ xprev) {
   constexpr int D = B - 1;
   constexpr int PW = R * B;
   constexpr int PS = PW + 1;
@@ -2460,7 +2493,24 @@ __global__ __launch_bounds__(64) void k_polar_comb(LaunchCtx c, const double* __
   // elementwise combination (updateV: V + gamma (X - Y), src/PGOAgent.cpp:1086-1091; updateY:
   // (1 - alpha) X + alpha V, :1077-1084; plain project: a0 A)
   auto comb = [&](double av, double bv, double cv) {
-    return Cv != nullptr ? av + b0 * (bv - cv) : (Bv != nullptr ? a0 * av + b0 * bv : a0 * av);
+    return Cv != nullptr ? av + b0 * (bv - cv) : (Bv != nullptr ? comb_xv(a0, av, b0, bv) : a0 * av);
+  };
+  auto project_span = [&]() {
+    if (t < count) {
+      double M[R][B];
+      double* ps = sm + t * PS;
+#pragma unroll
+      for (int cc = 0; cc < D; ++cc)
+#pragma unroll
+        for (int a = 0; a < R; ++a) M[a][cc] = ps[cc * R + a];
+#pragma unroll
+      for (int a = 0; a < R; ++a) M[a][D] = 0.0;
+      polar_fast<R, D>(M);  // the translation column passes through unchanged (stays in LDS)
+#pragma unroll
+      for (int cc = 0; cc < D; ++cc)
+#pragma unroll
+        for (int a = 0; a < R; ++a) ps[cc * R + a] = M[a][cc];
+    }
   };
   constexpr bool kVec = PW % 2 == 0;  // 16-byte chunks need an even pose width (aligned spans)
   if (kVec && count == 64) {
@@ -2500,21 +2550,7 @@ __global__ __launch_bounds__(64) void k_polar_comb(LaunchCtx c, const double* __
     }
   }
   __syncthreads();
-  if (t < count) {
-    double M[R][B];
-    double* ps = sm + t * PS;
-#pragma unroll
-    for (int cc = 0; cc < D; ++cc)
-#pragma unroll
-      for (int a = 0; a < R; ++a) M[a][cc] = ps[cc * R + a];
-#pragma unroll
-    for (int a = 0; a < R; ++a) M[a][D] = 0.0;
-    polar_fast<R, D>(M);  // the translation column passes through unchanged (stays in LDS)
-#pragma unroll
-    for (int cc = 0; cc < D; ++cc)
-#pragma unroll
-      for (int a = 0; a < R; ++a) ps[cc * R + a] = M[a][cc];
-  }
+  project_span();
   __syncthreads();
   if (kVec && count == 64) {
     constexpr int NV = PW / 2;
@@ -2533,11 +2569,49 @@ __global__ __launch_bounds__(64) void k_polar_comb(LaunchCtx c, const double* __
 #pragma unroll
       for (int i = 0; i < NV; ++i) P2[t + 64 * i] = vo[i];
     }
+    if constexpr (NEXT) {
+      // B again (the lines this block loaded above); each lane rewrites exactly the LDS words it read
+      const double2* B2 = reinterpret_cast<const double2*>(Bv + base);
+      if (xprev != nullptr) {
+        double2* XP = reinterpret_cast<double2*>(xprev + base);
+#pragma unroll
+        for (int i = 0; i < NV; ++i) XP[t + 64 * i] = vo[i];
+      }
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        const int x = 2 * (t + 64 * i);
+        double* dst = sm + (x / PW) * PS + x % PW;
+        const double2 bv = B2[t + 64 * i];
+        dst[0] = comb_xv(sa2, vo[i].x, sb2, bv.x);
+        dst[1] = comb_xv(sa2, vo[i].y, sb2, bv.y);
+      }
+      __syncthreads();
+      project_span();
+      __syncthreads();
+      double2* Y2 = reinterpret_cast<double2*>(ynext + base);
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        const int x = 2 * (t + 64 * i);
+        const double* src = sm + (x / PW) * PS + x % PW;
+        Y2[t + 64 * i] = make_double2(src[0], src[1]);
+      }
+    }
   } else {
     for (int x = t; x < total; x += 64) {
-      const double v = sm[(x / PW) * PS + x % PW];
+      double* src = sm + (x / PW) * PS + x % PW;
+      const double v = *src;
       out[base + x] = v;
       if (out2 != nullptr) out2[base + x] = v;
+      if constexpr (NEXT) {
+        if (xprev != nullptr) xprev[base + x] = v;
+        *src = comb_xv(sa2, v, sb2, Bv[base + x]);
+      }
+    }
+    if constexpr (NEXT) {
+      __syncthreads();
+      project_span();
+      __syncthreads();
+      for (int x = t; x < total; x += 64) ynext[base + x] = sm[(x / PW) * PS + x % PW];
     }
   }
 }
@@ -2547,11 +2621,16 @@ __global__ __launch_bounds__(64) void k_polar_comb(LaunchCtx c, const double* __
 //   out = project(sa X + sb V')     (updateY / the iterate(false) step, :1077-1084, of the next iteration)
 // V' is written back to V.  The combinations are the expressions k_polar_comb evaluates, so the
 // results are those of the two separate passes.
-template <int R, int B>
+// NEXT (TUNE_NEXT_Y, the engine's non-selected pass over the colour selected next): two more outputs from the
+// registers, the colour's next updateY and status reference,
+//   ynext = project(sa2 out + sb2 V')   and   xprev = out,
+// k_polar_comb's expressions on the values it would load back.  ynext may be the buffer Yv was read from.
+template <int R, int B, bool NEXT>
 __global__ __launch_bounds__(64) void k_polar_vnext(LaunchCtx c, const double* __restrict__ X,
                                                     double* __restrict__ V, const double* __restrict__ Yv,
                                                     double gv, double sa, double sb, double* __restrict__ out,
-                                                    double* __restrict__ xcopy) {
+                                                    double* __restrict__ xcopy, double sa2, double sb2, double* ynext,
+                                                    double* __restrict__ xprev) {
   constexpr int D = B - 1;
   constexpr int PW = R * B;
   constexpr int PS = PW + 1;
@@ -2617,16 +2696,41 @@ __global__ __launch_bounds__(64) void k_polar_vnext(LaunchCtx c, const double* _
       Vo[t + 64 * i] = v;
       src[0] = sa * vx[i].x + sb * v.x;
       src[1] = sa * vx[i].y + sb * v.y;
+      if constexpr (NEXT) vv[i] = v;  // V' stays in registers for ynext
     }
     __syncthreads();
     project_span();
     __syncthreads();
     double2* O2 = reinterpret_cast<double2*>(out + base);
+    if constexpr (NEXT) {
+      double2* XP = reinterpret_cast<double2*>(xprev + base);
 #pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int x = 2 * (t + 64 * i);
-      const double* src = sm + (x / PW) * PS + x % PW;
-      O2[t + 64 * i] = make_double2(src[0], src[1]);
+      for (int i = 0; i < NV; ++i) {
+        const int x = 2 * (t + 64 * i);
+        double* src = sm + (x / PW) * PS + x % PW;
+        const double2 xn = make_double2(src[0], src[1]);
+        O2[t + 64 * i] = xn;
+        if (xprev != nullptr) XP[t + 64 * i] = xn;
+        src[0] = comb_xv(sa2, xn.x, sb2, vv[i].x);
+        src[1] = comb_xv(sa2, xn.y, sb2, vv[i].y);
+      }
+      __syncthreads();
+      project_span();
+      __syncthreads();
+      double2* Y2n = reinterpret_cast<double2*>(ynext + base);
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        const int x = 2 * (t + 64 * i);
+        const double* src = sm + (x / PW) * PS + x % PW;
+        Y2n[t + 64 * i] = make_double2(src[0], src[1]);
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        const int x = 2 * (t + 64 * i);
+        const double* src = sm + (x / PW) * PS + x % PW;
+        O2[t + 64 * i] = make_double2(src[0], src[1]);
+      }
     }
   } else {
     for (int x = t; x < total; x += 64) {
@@ -2645,7 +2749,21 @@ __global__ __launch_bounds__(64) void k_polar_vnext(LaunchCtx c, const double* _
     __syncthreads();
     project_span();
     __syncthreads();
-    for (int x = t; x < total; x += 64) out[base + x] = sm[(x / PW) * PS + x % PW];
+    if constexpr (NEXT) {
+      for (int x = t; x < total; x += 64) {  // V[base + x] is this thread's own store above
+        double* src = sm + (x / PW) * PS + x % PW;
+        const double xn = *src;
+        out[base + x] = xn;
+        if (xprev != nullptr) xprev[base + x] = xn;
+        *src = comb_xv(sa2, xn, sb2, V[base + x]);
+      }
+      __syncthreads();
+      project_span();
+      __syncthreads();
+      for (int x = t; x < total; x += 64) ynext[base + x] = sm[(x / PW) * PS + x % PW];
+    } else {
+      for (int x = t; x < total; x += 64) out[base + x] = sm[(x / PW) * PS + x % PW];
+    }
   }
 }
 
@@ -4548,7 +4666,7 @@ template <int MODE>
 hipError_t spmm_mode(int r, int b, dim3 grid, const LaunchCtx& c, const QView& q, const SpmmArgs& a);
 
 #ifndef DPGO_SPMM_TU
-int g_tuning[TUNE_COUNT] = {0, -1, 1, 0, 0, 0, 0, 0, 0, 0, 1, 6, 1, 2};
+int g_tuning[TUNE_COUNT] = {0, -1, 1, 0, 0, 0, 0, 0, 0, 0, 1, 6, 1, 2, 1, 1};
 
 bool supported_rb(int r, int b) {
   if (b == 3) return r >= 2 && r <= 8;
@@ -4757,10 +4875,17 @@ hipError_t launch_tcg_updir(int r, int b, const LaunchCtx& c, const double* X, c
 
 hipError_t launch_retract(int r, int b, const LaunchCtx& c, const double* X, const double* V, double scale,
                           double* out, const double* g, const double* HV, const double* delta_impl,
-                          const double* status_ref) {
+                          const double* status_ref, const RetractTail* tail) {
   if (c.num_tiles == 0) return hipSuccess;
-  DPGO_DISPATCH(r, b, (k_retract<R, B><<<c.num_tiles, kThreads, 0, c.stream>>>(c, X, V, scale, out, g, HV, delta_impl,
-                                                                               status_ref)));
+  if (tail != nullptr) {
+    if (c.state == nullptr || tail->delta == nullptr || tail->Hdelta == nullptr || tail->peh == nullptr)
+      return hipErrorInvalidValue;
+    DPGO_DISPATCH(r, b, (k_retract<R, B, true><<<c.num_tiles, kThreads, 0, c.stream>>>(c, X, V, scale, out, g, HV,
+                                                                                       delta_impl, status_ref, *tail)));
+  } else {
+    DPGO_DISPATCH(r, b, (k_retract<R, B, false><<<c.num_tiles, kThreads, 0, c.stream>>>(
+                            c, X, V, scale, out, g, HV, delta_impl, status_ref, RetractTail{})));
+  }
   return hipGetLastError();
 }
 
@@ -4779,17 +4904,31 @@ hipError_t launch_precond(int r, int b, const LaunchCtx& c, const double* X, con
 
 hipError_t launch_polar_comb(int r, int b, const LaunchCtx& c, const double* A, const double* Bv,
                              const double* ca, const double* cb, double* out, const double* Cv, double sa,
-                             double sb, double* out2, double* xcopy) {
+                             double sb, double* out2, double* xcopy, const PolarNext* next) {
   if (c.num_tiles == 0) return hipSuccess;
-  DPGO_DISPATCH(r, b, (k_polar_comb<R, B><<<c.num_tiles, 64, 0, c.stream>>>(c, A, Bv, ca, cb, out, Cv, sa, sb, out2,
-                                                                             xcopy)));
+  if (next != nullptr) {  // the a0 A + b0 B form with uniform coefficients only
+    if (Bv == nullptr || Cv != nullptr || ca != nullptr || cb != nullptr || next->y == nullptr)
+      return hipErrorInvalidValue;
+    DPGO_DISPATCH(r, b, (k_polar_comb<R, B, true><<<c.num_tiles, 64, 0, c.stream>>>(
+                            c, A, Bv, ca, cb, out, Cv, sa, sb, out2, xcopy, next->sa, next->sb, next->y, next->xprev)));
+  } else {
+    DPGO_DISPATCH(r, b, (k_polar_comb<R, B, false><<<c.num_tiles, 64, 0, c.stream>>>(
+                            c, A, Bv, ca, cb, out, Cv, sa, sb, out2, xcopy, 0.0, 0.0, nullptr, nullptr)));
+  }
   return hipGetLastError();
 }
 
 hipError_t launch_polar_vnext(int r, int b, const LaunchCtx& c, const double* X, double* V, const double* Yv,
-                              double gv, double sa, double sb, double* out, double* xcopy) {
+                              double gv, double sa, double sb, double* out, double* xcopy, const PolarNext* next) {
   if (c.num_tiles == 0) return hipSuccess;
-  DPGO_DISPATCH(r, b, (k_polar_vnext<R, B><<<c.num_tiles, 64, 0, c.stream>>>(c, X, V, Yv, gv, sa, sb, out, xcopy)));
+  if (next != nullptr) {
+    if (next->y == nullptr) return hipErrorInvalidValue;
+    DPGO_DISPATCH(r, b, (k_polar_vnext<R, B, true><<<c.num_tiles, 64, 0, c.stream>>>(
+                            c, X, V, Yv, gv, sa, sb, out, xcopy, next->sa, next->sb, next->y, next->xprev)));
+  } else {
+    DPGO_DISPATCH(r, b, (k_polar_vnext<R, B, false><<<c.num_tiles, 64, 0, c.stream>>>(
+                            c, X, V, Yv, gv, sa, sb, out, xcopy, 0.0, 0.0, nullptr, nullptr)));
+  }
   return hipGetLastError();
 }
 

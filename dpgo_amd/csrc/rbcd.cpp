@@ -103,6 +103,17 @@ struct dpgo_rbcd_s {
   // colour's next combination pass (k_polar_vnext) with the gamma it was due with
   std::vector<char> v_pending;
   std::vector<double> v_gamma;
+  // TUNE_NEXT_Y: what the last dpgo_rbcd_pre_exchange's non-selected pass wrote ahead for the colour it predicted
+  // to be selected next -- that colour's updateY with the next iteration's alpha and (status on) its XPrev.  The next
+  // dpgo_rbcd_pre_exchange skips the selected colour's own pass only when the record matches exactly; everything
+  // that changes X, V, Y, XPrev or the coefficients in between clears it (set_X, set_selected) or fails the match.
+  struct NextY {
+    bool valid = false;
+    int color = -1;
+    double alpha = 0.0;
+    bool xprev = false;
+  } next_y;
+  long long next_y_skipped = 0, next_y_mispredicted = 0;  // selected passes skipped / records that did not match
   long iteration = 0;
   long long agent_updates = 0;
   // native exchange (dpgo_rbcd_comm_init / dpgo_rbcd_exchange): RCCL communicator over the ranks and
@@ -140,34 +151,43 @@ long color_first_pose(dpgo_rbcd e, int c) { return e->own_pose_off[e->color_off[
 long color_num_poses(dpgo_rbcd e, int c) { return e->own_pose_off[e->color_off[c + 1]] - e->own_pose_off[e->color_off[c]]; }
 double pose_bytes(dpgo_rbcd e) { return 8.0 * static_cast<double>(e->rb()); }
 
+// bytes of a PolarNext's extra outputs (ynext, and xprev when given), in pose vectors
+double next_vectors(const PolarNext* next) { return next ? 1.0 + (next->xprev ? 1.0 : 0.0) : 0.0; }
+
 int polar(dpgo_rbcd e, int c, const double* A, const double* B, double ca, double cb, double* out,
-          const double* C = nullptr, double* out2 = nullptr, double* xcopy = nullptr, hipStream_t on = nullptr) {
+          const double* C = nullptr, double* out2 = nullptr, double* xcopy = nullptr, hipStream_t on = nullptr,
+          const PolarNext* next = nullptr) {
   dpgo_hip_problem h = e->prob[c];
   if (!h) return DPGO_HIP_OK;
   // uniform Nesterov coefficients travel as kernel arguments
   auto ctx = make_ctx(h, FLAG_NONE, h->pa.p);
   if (on) ctx.stream = on;
-  HIP_TRY(launch_polar_comb(e->r, e->b, ctx, A, B, nullptr, nullptr, out, C, ca, cb, out2, xcopy));
+  HIP_TRY(launch_polar_comb(e->r, e->b, ctx, A, B, nullptr, nullptr, out, C, ca, cb, out2, xcopy, next));
   e->host_bytes += pose_bytes(e) * static_cast<double>(color_num_poses(e, c)) *
-                   (1.0 + (B ? 1.0 : 0.0) + (C ? 1.0 : 0.0) + 1.0 + (out2 ? 1.0 : 0.0) + (xcopy ? 1.0 : 0.0));
+                   (1.0 + (B ? 1.0 : 0.0) + (C ? 1.0 : 0.0) + 1.0 + (out2 ? 1.0 : 0.0) + (xcopy ? 1.0 : 0.0) +
+                    next_vectors(next));
   return DPGO_HIP_OK;
 }
 
 // out = project((1 - alpha) X + alpha V) for colour c, preceded by the colour's deferred updateV
 // V = project(V + gamma (X - Y)) in the same pass when one is pending.  xcopy: XPrev = X (the selected
 // colour's status reference) written from the same loads.
-int nesterov_comb(dpgo_rbcd e, int c, double* out, double* xcopy = nullptr, hipStream_t on = nullptr) {
+// next (the non-selected pass, out = X): also the colour's next updateY and XPrev from the same registers.
+int nesterov_comb(dpgo_rbcd e, int c, double* out, double* xcopy = nullptr, hipStream_t on = nullptr,
+                  const PolarNext* next = nullptr) {
   dpgo_hip_problem h = e->prob[c];
   if (!h) return DPGO_HIP_OK;
   double* Xc = color_ptr(e, e->X, c);
   double* Yc = color_ptr(e, e->Y, c);
   double* Vc = color_ptr(e, e->V, c);
-  if (!e->v_pending[c]) return polar(e, c, Xc, Vc, 1.0 - e->alpha, e->alpha, out, nullptr, nullptr, xcopy, on);
+  if (!e->v_pending[c])
+    return polar(e, c, Xc, Vc, 1.0 - e->alpha, e->alpha, out, nullptr, nullptr, xcopy, on, next);
   e->v_pending[c] = 0;
   auto ctx = make_ctx(h, FLAG_NONE, h->pa.p);
   if (on) ctx.stream = on;
-  HIP_TRY(launch_polar_vnext(e->r, e->b, ctx, Xc, Vc, Yc, e->v_gamma[c], 1.0 - e->alpha, e->alpha, out, xcopy));
-  e->host_bytes += pose_bytes(e) * static_cast<double>(color_num_poses(e, c)) * (5.0 + (xcopy ? 1.0 : 0.0));
+  HIP_TRY(launch_polar_vnext(e->r, e->b, ctx, Xc, Vc, Yc, e->v_gamma[c], 1.0 - e->alpha, e->alpha, out, xcopy, next));
+  e->host_bytes += pose_bytes(e) * static_cast<double>(color_num_poses(e, c)) *
+                   (5.0 + (xcopy ? 1.0 : 0.0) + next_vectors(next));
   return DPGO_HIP_OK;
 }
 
@@ -808,6 +828,7 @@ int dpgo_rbcd_set_X(dpgo_rbcd e, const double* Xg) {
   e->alpha = 0.0;
   e->iteration = 0;
   e->last_color = -1;
+  e->next_y.valid = false;
   std::fill(e->v_pending.begin(), e->v_pending.end(), 0);
   return DPGO_HIP_OK;
 }
@@ -838,6 +859,8 @@ int dpgo_rbcd_pre_exchange(dpgo_rbcd e, int color) {
   // halo, so every colour order (the cyclic schedule, the example's greedy robot) and every rank count give
   // bitwise the same weights.
   e->last_color = color;
+  const dpgo_rbcd_s::NextY pre = e->next_y;  // what the previous call wrote ahead; consumed or dropped here
+  e->next_y.valid = false;
   e->iteration += 1;  // mIterationNumber++ (:643)
   // shouldUpdateLoopClosureWeights (:1174-1179): every agent reweights at the start of its iterate;
   // the non-selected ones here, the selected ones in dpgo_rbcd_update once their neighbours' poses
@@ -876,11 +899,50 @@ int dpgo_rbcd_pre_exchange(dpgo_rbcd e, int color) {
     HIP_TRY(hipStreamWaitEvent(e->side, e->ev_start, 0));
     on = e->side;
   }
+  // TUNE_NEXT_Y (one rank only: with a side stream the selected colour's pass overlaps the halo and stays as it
+  // is).  Use: the previous call's non-selected pass already wrote this colour's Y (and XPrev) for exactly this
+  // iteration -- same colour, bit-equal alpha, the same XPrev decision, and nothing since has reset or replaced X,
+  // V, Y or XPrev (a restart or a reweighting in this call, set_X, set_selected).  Otherwise today's pass runs and
+  // overwrites both.
+  const bool next_y_on = e->prob[color] && !e->side && e->prob[color]->tuning[TUNE_NEXT_Y] > 0;
+  const bool want_xprev = e->P.status && !restart;
+  const bool reset_now = e->gnc_due && e->P.acceleration;  // initializeAcceleration above: Y = X, alpha = 0
+  bool skip_selected = false;
+  if (pre.valid) {
+    skip_selected = next_y_on && pre.color == color && !restart && !reset_now && !e->v_pending[color] &&
+                    pre.xprev == want_xprev && std::memcmp(&pre.alpha, &e->alpha, sizeof(double)) == 0;
+    if (skip_selected)
+      e->next_y_skipped += 1;
+    else
+      e->next_y_mispredicted += 1;
+  }
+  // Predict: the cyclic schedule selects (color + 1) % ncolors next; its alpha follows from the iteration count
+  // alone (updateGamma / updateAlpha), unless that iteration restarts or reweights (initializeAcceleration) or this
+  // one restarts (X is replaced by XPrev below, gamma is reset by the update).
+  const int next_color = (color + 1) % e->ncolors;
+  PolarNext next{0.0, 0.0, nullptr, nullptr};
+  bool predict = false;
+  if (next_y_on && next_color != color && e->prob[next_color] && !restart) {
+    const bool next_restart = (e->iteration + 2) % e->P.restart_interval == 0;
+    const bool next_gnc = e->P.robust_cost != DPGO_ROBUST_L2 && (e->iteration + 2) % e->P.robust_opt_inner_iters == 0;
+    if (!next_restart && !next_gnc) {
+      const double gamma_next = (1.0 + std::sqrt(1.0 + 4.0 * N * N * e->gamma * e->gamma)) / (2.0 * N);
+      const double alpha_next = 1.0 / (gamma_next * N);
+      next = PolarNext{1.0 - alpha_next, alpha_next, color_ptr(e, e->Y, next_color),
+                       e->P.status ? color_ptr(e, e->Xprev, next_color) : nullptr};
+      predict = true;
+      e->next_y.valid = true;
+      e->next_y.color = next_color;
+      e->next_y.alpha = alpha_next;
+      e->next_y.xprev = e->P.status != 0;
+    }
+  }
   for (int c = 0; c < e->ncolors; ++c) {
     if (!e->prob[c]) continue;
     double* Xc = color_ptr(e, e->X, c);
     double* Yc = color_ptr(e, e->Y, c);
     if (c == color) {
+      if (skip_selected) continue;  // Y and XPrev are in place (see above)
       // updateY (selected); XPrev = X (:673) for the status, written from the same loads (a restart
       // iteration already copied every X above)
       DPGO_TRY(nesterov_comb(e, c, Yc, e->P.status && !restart ? color_ptr(e, e->Xprev, c) : nullptr, on));
@@ -895,7 +957,7 @@ int dpgo_rbcd_pre_exchange(dpgo_rbcd e, int color) {
     // pack read X, and Y is not stored); updateV: V = project(V + gamma (X - Y)) = project(V)
     // because X == Y exactly, and V already lies on the manifold (a previous project() output), so
     // that pass is skipped.  A deferred updateV of this colour's last update runs in the same pass.
-    DPGO_TRY(nesterov_comb(e, c, Xc));
+    DPGO_TRY(nesterov_comb(e, c, Xc, nullptr, nullptr, predict && c == next_color ? &next : nullptr));
     if (restart) {  // restartNesterovAcceleration(false): X = XPrev, V = Y = X (Y implied, as above)
       DPGO_TRY(copy_poses(e, e->X.p, e->Xprev.p, color_first_pose(e, c), color_num_poses(e, c)));
       DPGO_TRY(copy_poses(e, e->V.p, e->X.p, color_first_pose(e, c), color_num_poses(e, c)));
@@ -941,6 +1003,7 @@ static int update_body(dpgo_rbcd e, int color, dpgo_opt_result* results);
 
 int dpgo_rbcd_set_selected(dpgo_rbcd e, const int* agent_mask) {
   if (!e) return fail(DPGO_HIP_EINVAL, "null engine");
+  e->next_y.valid = false;  // the caller left the colour schedule: the next selected pass runs itself
   if (!agent_mask) {
     e->sel_mask.clear();
     return DPGO_HIP_OK;
@@ -1138,6 +1201,9 @@ int dpgo_rbcd_bytes(dpgo_rbcd e, double* bytes, double* evaltcg_bytes_per_color)
         // a CG step that continues also reads r, X, Minv and writes r, delta
         total += (cg + bnd - impl) * z.n * 4.0 * P - runs * z.n * P;
         total += std::max(0.0, cg - lcon - maxit) * z.n * (4.0 * P + DW);
+        // TUNE_TAIL_FUSE: a Run's last step applied by the retraction (AgentState::st_tail counts them) -- no
+        // k_tcg_updir pass (eta read and written); the retraction reads delta and Hdelta beside eta
+        total -= static_cast<double>(h->h_state[a].st_tail) * z.n * 2.0 * P;
       } else {
         // tCG updates: a CG step reads delta, Hdelta, eta, r, X, Minv and writes eta, r, z; a boundary step
         // reads delta, Hdelta, eta and writes eta (the first step of a tCG reads no eta)
@@ -1263,6 +1329,13 @@ int dpgo_rbcd_bench_hvp(dpgo_rbcd e, int color, int reps, double* ms) {
   }
   DPGO_TRY(ensure_work_public(h));
   return dpgo_hip_bench_hvp(h, color_ptr(e, e->X, color), h->tA.p, h->tB.p, reps, ms);
+}
+
+int dpgo_rbcd_next_y_counters(dpgo_rbcd e, long long* skipped, long long* mispredicted) {
+  if (!e) return fail(DPGO_HIP_EINVAL, "null engine");
+  if (skipped) *skipped = e->next_y_skipped;
+  if (mispredicted) *mispredicted = e->next_y_mispredicted;
+  return DPGO_HIP_OK;
 }
 
 int dpgo_rbcd_counters(dpgo_rbcd e, long long* agent_updates, long long* iterations) {

@@ -553,6 +553,7 @@ _SIGS2 = [
     ("dpgo_rbcd_set_selected", [C.c_void_p, _ip], C.c_int),
     ("dpgo_rbcd_bench_spmm", [C.c_void_p, C.c_int, C.c_int, _dp, _dp], C.c_int),
     ("dpgo_rbcd_counters", [C.c_void_p, _lp, _lp], C.c_int),
+    ("dpgo_rbcd_next_y_counters", [C.c_void_p, _lp, _lp], C.c_int),
     ("dpgo_rbcd_spmm_bytes", [C.c_void_p, C.c_int, _dp, _dp], C.c_int),
     ("dpgo_rbcd_bench_hvp", [C.c_void_p, C.c_int, C.c_int, _dp], C.c_int),
     ("dpgo_rbcd_reset_stream", [C.c_void_p], C.c_int),
@@ -1043,3 +1044,10 @@ class Rbcd:
         a, i = C.c_longlong(), C.c_longlong()
         _check(lib().dpgo_rbcd_counters(self.h, C.byref(a), C.byref(i)))
         return a.value, i.value
+
+    def next_y_counters(self):
+        """(skipped, mispredicted): selected-colour combination passes skipped because the previous iteration's
+        non-selected pass wrote their outputs ahead (tuning key 15), and write-ahead records that were dropped."""
+        s, m = C.c_longlong(), C.c_longlong()
+        _check(lib().dpgo_rbcd_next_y_counters(self.h, C.byref(s), C.byref(m)))
+        return s.value, m.value

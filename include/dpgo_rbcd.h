@@ -192,6 +192,10 @@ int dpgo_rbcd_spmm_bytes(dpgo_rbcd e, int color, double* bsr_bytes, double* form
 int dpgo_rbcd_bench_hvp(dpgo_rbcd e, int color, int reps, double* ms);
 /* SpMM / HVP launches issued so far (for throughput accounting) */
 int dpgo_rbcd_counters(dpgo_rbcd e, long long* agent_updates, long long* iterations);
+/* Tuning key 15 (next-Y fusion): selected-colour combination passes skipped because the previous iteration's
+   non-selected pass had already written that colour's Y / XPrev, and write-ahead records that did not match the
+   next call (another colour, a restart or reweighting, another alpha) and were dropped.  Either may be null. */
+int dpgo_rbcd_next_y_counters(dpgo_rbcd e, long long* skipped, long long* mispredicted);
 
 /* Central evaluation (examples/MultiRobotExample.cpp:229-235): this rank's share of the whole-graph
  * cost f(X) = 1/2 <X Q, X> (sum over ranks = the central cost; Q is the dataset's, unit weights, as the
