@@ -83,6 +83,12 @@ class PGOAgent {
   bool getTrajectoryInLocalFrame(Matrix& Trajectory);
   Matrix localPoseGraphOptimization();
   void setGlobalAnchor(const Matrix& M) { globalAnchor = M; }
+  // In the frame of the global anchor (reference include/DPGO/PGOAgent.h:213-240, src/PGOAgent.cpp:500-562): false
+  // without an anchor or before initialisation.  The trajectory is rounded on the GPU (dpgo_hip_round_se); the
+  // single-pose getters return Y_a^T X_i with the translation re-centred and do not project the rotation.
+  bool getTrajectoryInGlobalFrame(Matrix& Trajectory);
+  bool getPoseInGlobalFrame(unsigned poseID, Matrix& T);
+  bool getNeighborPoseInGlobalFrame(unsigned neighborID, unsigned poseID, Matrix& T);
   // robust global-frame initialisation (reference include/DPGO/PGOAgent.h:449-474)
   Matrix computeNeighborTransform(const PoseID& nID, const Matrix& var);
   Matrix computeRobustNeighborTransformTwoStage(unsigned neighborID, const PoseDict& poseDict);

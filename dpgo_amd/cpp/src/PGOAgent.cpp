@@ -321,6 +321,41 @@ bool PGOAgent::getTrajectoryInLocalFrame(Matrix& Trajectory) {  // :481-498
   return true;
 }
 
+bool PGOAgent::getTrajectoryInGlobalFrame(Matrix& Trajectory) {  // :500-519
+  if (!globalAnchor || mState != INITIALIZED) return false;
+  const Matrix& A = *globalAnchor;
+  if (A.rows() != static_cast<long>(r) || A.cols() != static_cast<long>(d + 1))
+    throw std::invalid_argument("getTrajectoryInGlobalFrame: the global anchor must be r x (d+1)");
+  Matrix T(d, static_cast<long>(n) * (d + 1));
+  if (dpgo_hip_round_se(static_cast<int>(r), static_cast<int>(d), static_cast<int>(n), X.data(), A.data(),
+                        T.data()) != DPGO_HIP_OK)
+    throw std::runtime_error(std::string("getTrajectoryInGlobalFrame: ") + dpgo_hip_last_error());
+  Trajectory = T;
+  return true;
+}
+
+// Y_a^T Xi with the translation relative to the anchor's; the rotation block is left as it is (:521-562)
+static Matrix poseInAnchorFrame(const Matrix& A, const Matrix& Xi, unsigned d) {
+  const Matrix YaT = A.block(0, 0, A.rows(), d).transpose();
+  Matrix Ti = YaT * Xi;
+  Ti.setBlock(0, d, Ti.block(0, d, d, 1) - YaT * A.block(0, d, A.rows(), 1));
+  return Ti;
+}
+
+bool PGOAgent::getPoseInGlobalFrame(unsigned poseID, Matrix& T) {  // :521-538
+  if (!globalAnchor || mState != INITIALIZED || poseID >= n) return false;
+  T = poseInAnchorFrame(*globalAnchor, X.block(0, poseID * (d + 1), r, d + 1), d);
+  return true;
+}
+
+bool PGOAgent::getNeighborPoseInGlobalFrame(unsigned neighborID, unsigned poseID, Matrix& T) {  // :540-562
+  if (!globalAnchor || mState != INITIALIZED) return false;
+  const auto it = neighborPoseDict.find(PoseID(neighborID, poseID));
+  if (it == neighborPoseDict.end()) return false;
+  T = poseInAnchorFrame(*globalAnchor, it->second, d);
+  return true;
+}
+
 void PGOAgent::constructQMatrix() {  // :720-781
   std::vector<RelativeSEMeasurement> priv = odometry;
   priv.insert(priv.end(), privateLoopClosures.begin(), privateLoopClosures.end());

@@ -2577,6 +2577,36 @@ int dpgo_hip_project_polar(int r, int d, int n, const double* in, double* out) {
   return stateless(r, d, n, in, nullptr, 1.0, out, 2);
 }
 
+int dpgo_hip_round_se_dev(int r, int d, long long n, const double* X_dev, const double* anchor_dev, double* T_dev,
+                          void* stream) {
+  if ((d != 2 && d != 3) || r < d || !dpgo::supported_rb(r, d + 1))
+    return fail(DPGO_HIP_EINVAL, "round_se: unsupported (r, d)");
+  if (n <= 0) return fail(DPGO_HIP_EINVAL, "round_se: need n >= 1 poses");
+  if (!X_dev || !T_dev) return fail(DPGO_HIP_EINVAL, "round_se: null X or T");
+  if (usable_devices() == 0) return fail(DPGO_HIP_ENODEV, "no gfx950 device available (no CPU fallback)");
+  HIP_TRY(dpgo::launch_round_se(r, d + 1, static_cast<long>(n), X_dev, anchor_dev, T_dev,
+                                static_cast<hipStream_t>(stream)));
+  return DPGO_HIP_OK;
+}
+
+int dpgo_hip_round_se(int r, int d, int n, const double* X, const double* anchor, double* T) {
+  if ((d != 2 && d != 3) || r < d || !dpgo::supported_rb(r, d + 1))
+    return fail(DPGO_HIP_EINVAL, "round_se: unsupported (r, d)");
+  if (n <= 0) return fail(DPGO_HIP_EINVAL, "round_se: need n >= 1 poses");
+  if (!X || !T) return fail(DPGO_HIP_EINVAL, "round_se: null X or T");
+  if (usable_devices() == 0) return fail(DPGO_HIP_ENODEV, "no gfx950 device available (no CPU fallback)");
+  const size_t rb = static_cast<size_t>(r) * (d + 1), db = static_cast<size_t>(d) * (d + 1);
+  dpgo::DevBuf<double> x, a, t;
+  HIP_TRY(x.ensure(rb * n));
+  HIP_TRY(t.ensure(db * n));
+  if (anchor) HIP_TRY(a.ensure(rb));
+  hipStream_t s = nullptr;
+  HIP_TRY(hipMemcpyAsync(x.p, X, sizeof(double) * rb * n, hipMemcpyHostToDevice, s));
+  if (anchor) HIP_TRY(hipMemcpyAsync(a.p, anchor, sizeof(double) * rb, hipMemcpyHostToDevice, s));
+  DPGO_TRY(dpgo_hip_round_se_dev(r, d, n, x.p, anchor ? a.p : nullptr, t.p, s));
+  return download(T, t.p, db * n, s);
+}
+
 // ----------------------------------------------------------------------- certification
 }  // extern "C"
 

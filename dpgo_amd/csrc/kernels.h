@@ -444,6 +444,12 @@ hipError_t launch_polar_comb(int r, int b, const LaunchCtx& c, const double* A, 
                              const double* ca, const double* cb, double* out, const double* Cv = nullptr,
                              double sa = 1.0, double sb = 0.0, double* out2 = nullptr, double* xcopy = nullptr,
                              const PolarNext* next = nullptr);
+// T (d x b per pose, column-major, pose-major) = SE(d) rounding of the n lifted poses X (r x b per pose) in the frame
+// of the lifted pose `anchor` (r x b; null = pose 0 of X): R_j = projectToRotationGroup(Y_a^T Y_j),
+// t_j = Y_a^T p_j - Y_a^T p_a (PGOAgent::getTrajectoryInGlobalFrame / InLocalFrame, src/PGOAgent.cpp:481-519).
+// No tile set: any n >= 1; T must not overlap X.
+hipError_t launch_round_se(int r, int b, long n, const double* X, const double* anchor, double* T,
+                           hipStream_t stream);
 // PGOAgent::computeConvergedLoopClosureRatio (src/PGOAgent.cpp:1247-1289): per agent a, the share of
 // its loop closures idx[off[a] .. off[a+1]) whose weight w[] is exactly 1 or 0 (0/0 = NaN, as there)
 hipError_t launch_conv_ratio(int num_agents, const int* off, const int* idx, const double* w, double* ratio,

@@ -2616,6 +2616,101 @@ __global__ __launch_bounds__(64) void k_polar_comb(LaunchCtx c, const double* __
   }
 }
 
+// SE(d) rounding of lifted poses in the frame of an anchor pose A = [Y_a | p_a] (PGOAgent::getTrajectoryInGlobalFrame,
+// src/PGOAgent.cpp:500-519; anchor = pose 0 of X: getTrajectoryInLocalFrame, :481-498): per pose j
+//   R_j = projectToRotationGroup(Y_a^T Y_j),   t_j = Y_a^T p_j - Y_a^T p_a,
+// written as [R_j | t_j], d x (d+1) column-major, pose-major.  A streaming pass with no tile set and no agent state:
+// block k takes poses [64 k, 64 k + 64) -- one contiguous span of 64 r b doubles in, 64 d b doubles out.  As in
+// k_polar_comb the span streams through LDS with coalesced loads (16-byte chunks on a full block when the span is
+// aligned), thread t rounds pose t from LDS (row stride r b + 1 doubles: conflict-free b64 reads), and the rounded
+// poses stream back out of the same LDS (row stride d b + 1) coalesced.
+template <int R, int B>
+__global__ __launch_bounds__(64) void k_round_se(long n, const double* __restrict__ X,
+                                                 const double* __restrict__ anchor, double* __restrict__ T) {
+  constexpr int D = B - 1;
+  constexpr int PW = R * B, PS = PW + 1;
+  constexpr int OW = D * B, OS = OW + 1;
+  static_assert(OS <= PS, "the rounded poses reuse the staged span's LDS");
+  __shared__ double sm[64 * PS];
+  const int t = static_cast<int>(threadIdx.x);
+  const long first = static_cast<long>(blockIdx.x) * 64;
+  if (first >= n) return;
+  const int count = n - first < 64 ? static_cast<int>(n - first) : 64;
+  const double* src = X + first * PW;
+  double* dst = T + first * OW;
+  const int total = count * PW;
+  const bool full = count == 64;
+  if (PW % 2 == 0 && full && (reinterpret_cast<unsigned long>(src) & 15) == 0) {
+    constexpr int NV = PW / 2;  // 16-byte chunks per lane (PW even: a chunk never straddles two poses)
+    const double2* S2 = reinterpret_cast<const double2*>(src);
+    double2 v[NV];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) v[i] = S2[t + 64 * i];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int x = 2 * (t + 64 * i);
+      double* q = sm + (x / PW) * PS + x % PW;
+      q[0] = v[i].x;
+      q[1] = v[i].y;
+    }
+  } else {
+    for (int x = t; x < total; x += 64) sm[(x / PW) * PS + x % PW] = src[x];
+  }
+  __syncthreads();
+  const bool own = t < count;
+  double W[D][D], tv[D];
+  if (own) {
+    const double* ps = sm + t * PS;
+    // the anchor is read at block-uniform addresses: r b doubles, once per wave
+    double ta[D];
+#pragma unroll
+    for (int a = 0; a < D; ++a) {
+#pragma unroll
+      for (int c = 0; c < D; ++c) {
+        double s = 0.0;
+#pragma unroll
+        for (int k = 0; k < R; ++k) s = fma(anchor[a * R + k], ps[c * R + k], s);
+        W[a][c] = s;
+      }
+      double sp = 0.0, sa = 0.0;
+#pragma unroll
+      for (int k = 0; k < R; ++k) {
+        sp = fma(anchor[a * R + k], ps[D * R + k], sp);
+        sa = fma(anchor[a * R + k], anchor[D * R + k], sa);
+      }
+      tv[a] = sp;
+      ta[a] = sa;
+    }
+#pragma unroll
+    for (int a = 0; a < D; ++a) tv[a] -= ta[a];
+  }
+  __syncthreads();  // every pose of the span is in registers: its LDS now takes the rounded poses
+  if (own) {
+    rotation_project<D>(W);
+    double* po = sm + t * OS;
+#pragma unroll
+    for (int c = 0; c < D; ++c)
+#pragma unroll
+      for (int a = 0; a < D; ++a) po[c * D + a] = W[a][c];
+#pragma unroll
+    for (int a = 0; a < D; ++a) po[D * D + a] = tv[a];
+  }
+  __syncthreads();
+  if (full && (reinterpret_cast<unsigned long>(dst) & 15) == 0) {
+    constexpr int NO = OW / 2;  // OW = d (d + 1) is even
+    double2* O2 = reinterpret_cast<double2*>(dst);
+#pragma unroll
+    for (int i = 0; i < NO; ++i) {
+      const int x = 2 * (t + 64 * i);
+      const double* q = sm + (x / OW) * OS + x % OW;
+      O2[t + 64 * i] = make_double2(q[0], q[1]);
+    }
+  } else {
+    const int total_out = count * OW;
+    for (int x = t; x < total_out; x += 64) dst[x] = sm[(x / OW) * OS + x % OW];
+  }
+}
+
 // Nesterov updateV deferred into the colour's next combination pass (one pass instead of two):
 //   V' = project(V + gv (X - Yv))   (updateV, src/PGOAgent.cpp:1086-1091, of the agent's last update)
 //   out = project(sa X + sb V')     (updateY / the iterate(false) step, :1077-1084, of the next iteration)
@@ -4929,6 +5024,17 @@ hipError_t launch_polar_vnext(int r, int b, const LaunchCtx& c, const double* X,
     DPGO_DISPATCH(r, b, (k_polar_vnext<R, B, false><<<c.num_tiles, 64, 0, c.stream>>>(
                             c, X, V, Yv, gv, sa, sb, out, xcopy, 0.0, 0.0, nullptr, nullptr)));
   }
+  return hipGetLastError();
+}
+
+hipError_t launch_round_se(int r, int b, long n, const double* X, const double* anchor, double* T,
+                           hipStream_t stream) {
+  if (n <= 0 || X == nullptr || T == nullptr) return hipErrorInvalidValue;
+  const long blocks = (n + 63) / 64;
+  if (blocks > 0x7fffffffL) return hipErrorInvalidValue;
+  const dim3 grid(static_cast<unsigned>(blocks));
+  const double* A = anchor != nullptr ? anchor : X;  // the local frame: pose 0 of X
+  DPGO_DISPATCH(r, b, (k_round_se<R, B><<<grid, 64, 0, stream>>>(n, X, A, T)));
   return hipGetLastError();
 }
 

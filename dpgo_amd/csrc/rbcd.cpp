@@ -121,6 +121,18 @@ struct dpgo_rbcd_s {
   ncclComm_t comm = nullptr;
   bool own_comm = false;
   DevBuf<double> xsend, xrecv;
+  // solution readout (dpgo_rbcd_get_anchor / _get_trajectory / _get_weights)
+  int n_global = 0;
+  std::vector<int> own_of_global;  // global pose id -> owned buffer pose index, -1 = another rank's
+  DevBuf<double> Tround;           // the owned poses rounded to SE(d), d x b per pose
+  // per colour: the problem edges whose weight this rank reports (dpgo_rbcd_weight_owner's rule: private loop
+  // closures and the shared ones whose other agent has the larger ID) with their index in the graph's edge order
+  struct WMap {
+    std::vector<int> prob_edge, graph_edge;
+    long prob_edges = 0;  // length of the colour's w_prob
+  };
+  std::vector<WMap> wmap;
+  std::vector<int> odo_edges;  // graph edges that are odometry of an owned agent: weight 1, never reweighted
 
   ~dpgo_rbcd_s();
   void release() {
@@ -473,6 +485,10 @@ int dpgo_rbcd_create(dpgo_graph g, int num_agents, const int* agent_of_pose, con
     const int q = owned_pos[agent_of_pose[i]];
     if (q >= 0) e->own_global[e->own_pose_off[q] + local[i]] = i;
   }
+  e->n_global = n;
+  e->own_of_global.assign(n, -1);
+  for (long q = 0; q < e->Nown; ++q) e->own_of_global[e->own_global[q]] = static_cast<int>(q);
+  e->wmap.assign(e->ncolors, {});
   auto owned_index = [&](int pose) -> long {
     const int q = owned_pos[agent_of_pose[pose]];
     return q < 0 ? -1 : e->own_pose_off[q] + local[pose];
@@ -667,12 +683,18 @@ int dpgo_rbcd_create(dpgo_graph g, int num_agents, const int* agent_of_pose, con
         const bool own_i = agent_of_pose[i] == A, own_j = agent_of_pose[j] == A;
         int ge = -1;
         if (own_i && own_j) {
-          if (local[j] == local[i] + 1) continue;  // odometry: never reweighted
+          if (local[j] == local[i] + 1) {  // odometry: never reweighted
+            e->odo_edges.push_back(static_cast<int>(k));
+            continue;
+          }
         } else {
           const int other = own_i ? agent_of_pose[j] : agent_of_pose[i];
           if (other < A) continue;  // the lower-ID agent is responsible (:1201-1235)
           ge = g_index.at(k);
         }
+        // the weight dpgo_rbcd_get_weights reports for graph edge k: this agent's copy
+        e->wmap[c].prob_edge.push_back(static_cast<int>(prob_edges + static_cast<long>(x)));
+        e->wmap[c].graph_edge.push_back(static_cast<int>(k));
         auto src_of = [&](int pose) -> int {
           const long oi = owned_index(pose);
           return oi >= 0 ? static_cast<int>(oi) : -1 - static_cast<int>(recv_slot.at(pose));
@@ -716,6 +738,7 @@ int dpgo_rbcd_create(dpgo_graph g, int num_agents, const int* agent_of_pose, con
     if (rc == DPGO_HIP_OK) rc = upload_vec(t->tau, tauv, e->stream);
     if (rc == DPGO_HIP_OK) rc = upload_vec(t->w, wv, e->stream);
     auto* gc = e->gnc[c];
+    e->wmap[c].prob_edges = prob_edges;
     gc->n = static_cast<int>(gn_pe.size());
     if (rc == DPGO_HIP_OK) rc = upload_vec(gc->prob_edge, gn_pe, e->stream);
     if (rc == DPGO_HIP_OK) rc = upload_vec(gc->g_entry, gn_ge, e->stream);
@@ -844,6 +867,82 @@ int dpgo_rbcd_get_X(dpgo_rbcd e, double* Xg) {
   }
   for (long q = 0; q < e->Nown; ++q)
     std::memcpy(Xg + static_cast<size_t>(e->own_global[q]) * rbs, &host[q * rbs], sizeof(double) * rbs);
+  return DPGO_HIP_OK;
+}
+
+int dpgo_rbcd_get_anchor(dpgo_rbcd e, int pose, double* anchor, int* owned) {
+  if (!e || !anchor || !owned) return fail(DPGO_HIP_EINVAL, "null argument");
+  if (pose < 0 || pose >= e->n_global) return fail(DPGO_HIP_EINVAL, "anchor pose out of range");
+  const int q = e->own_of_global[pose];
+  *owned = q >= 0 ? 1 : 0;
+  if (q < 0) return DPGO_HIP_OK;
+  DPGO_TRY(join_side(e));
+  const size_t rbs = e->rb();
+  HIP_TRY(hipMemcpyAsync(anchor, e->X.p + static_cast<size_t>(q) * rbs, sizeof(double) * rbs, hipMemcpyDeviceToHost,
+                         e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return DPGO_HIP_OK;
+}
+
+int dpgo_rbcd_get_trajectory(dpgo_rbcd e, const double* anchor, double* Tg) {
+  if (!e || !Tg) return fail(DPGO_HIP_EINVAL, "null argument");
+  if (!anchor && e->own_of_global[0] < 0)
+    return fail(DPGO_HIP_EINVAL, "no anchor given and global pose 0 belongs to another rank (dpgo_rbcd_get_anchor)");
+  if (e->Nown == 0) return DPGO_HIP_OK;
+  DPGO_TRY(join_side(e));
+  const size_t rbs = e->rb(), dbs = static_cast<size_t>(e->d) * e->b;
+  // the anchor on the device: the caller's (r b doubles, staged behind the rounded poses) or the engine's own pose 0
+  HIP_TRY(e->Tround.ensure(static_cast<size_t>(e->Nown) * dbs + rbs));
+  const double* anchor_dev = e->X.p + static_cast<size_t>(anchor ? 0 : e->own_of_global[0]) * rbs;
+  if (anchor) {
+    double* stage = e->Tround.p + static_cast<size_t>(e->Nown) * dbs;
+    HIP_TRY(hipMemcpyAsync(stage, anchor, sizeof(double) * rbs, hipMemcpyHostToDevice, e->stream));
+    anchor_dev = stage;
+  }
+  DPGO_TRY(dpgo_hip_round_se_dev(e->r, e->d, e->Nown, e->X.p, anchor_dev, e->Tround.p, e->stream));
+  std::vector<double> host(static_cast<size_t>(e->Nown) * dbs);
+  HIP_TRY(hipMemcpyAsync(host.data(), e->Tround.p, sizeof(double) * host.size(), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  for (long q = 0; q < e->Nown; ++q)
+    std::memcpy(Tg + static_cast<size_t>(e->own_global[q]) * dbs, &host[q * dbs], sizeof(double) * dbs);
+  return DPGO_HIP_OK;
+}
+
+int dpgo_rbcd_get_weights(dpgo_rbcd e, double* w) {
+  if (!e || !w) return fail(DPGO_HIP_EINVAL, "null argument");
+  for (int k : e->odo_edges) w[k] = 1.0;
+  const bool l2 = e->P.robust_cost == DPGO_ROBUST_L2;  // never reweighted: no device read
+  std::vector<double> host;
+  for (int c = 0; c < e->ncolors; ++c) {
+    const auto& M = e->wmap[c];
+    if (M.graph_edge.empty()) continue;
+    if (!l2) {
+      host.resize(static_cast<size_t>(M.prob_edges));
+      HIP_TRY(hipMemcpyAsync(host.data(), e->gnc[c]->w_prob.p, sizeof(double) * host.size(), hipMemcpyDeviceToHost,
+                             e->stream));
+      HIP_TRY(hipStreamSynchronize(e->stream));
+    }
+    for (size_t x = 0; x < M.graph_edge.size(); ++x) w[M.graph_edge[x]] = l2 ? 1.0 : host[M.prob_edge[x]];
+  }
+  return DPGO_HIP_OK;
+}
+
+int dpgo_rbcd_weight_owner(dpgo_graph g, int num_agents, const int* agent_of_pose, int* owner) {
+  if (!g || !agent_of_pose || !owner || num_agents <= 0) return fail(DPGO_HIP_EINVAL, "bad weight_owner arguments");
+  std::vector<int> local(g->n), count(num_agents, 0);
+  for (int i = 0; i < g->n; ++i) {
+    const int a = agent_of_pose[i];
+    if (a < 0 || a >= num_agents) return fail(DPGO_HIP_EINVAL, "agent_of_pose out of range");
+    local[i] = count[a]++;
+  }
+  for (size_t k = 0; k < g->p1.size(); ++k) {
+    const int i = g->p1[k], j = g->p2[k];
+    const int ai = agent_of_pose[i], aj = agent_of_pose[j];
+    if (ai == aj)
+      owner[k] = local[j] == local[i] + 1 ? -1 : ai;
+    else
+      owner[k] = std::min(ai, aj);
+  }
   return DPGO_HIP_OK;
 }
 

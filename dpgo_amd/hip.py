@@ -75,6 +75,9 @@ _SIGS = [
     ("dpgo_hip_tangent_project", [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp], C.c_int),
     ("dpgo_hip_retract_qf", [C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_double, _dp], C.c_int),
     ("dpgo_hip_project_polar", [C.c_int, C.c_int, C.c_int, _dp, _dp], C.c_int),
+    ("dpgo_hip_round_se", [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp], C.c_int),
+    ("dpgo_hip_round_se_dev", [C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+     C.c_int),
     ("dpgo_hip_optimize", [C.c_void_p, C.POINTER(OptParams), _dp, _dp, C.POINTER(OptResult)], C.c_int),
     ("dpgo_hip_f_dev", [C.c_void_p, C.c_void_p, _dp], C.c_int),
     ("dpgo_hip_egrad_dev", [C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
@@ -488,6 +491,26 @@ def project_polar(M, d):
     return from_dev_layout(o, r)
 
 
+def round_se(X, d, anchor=None):
+    """SE(d) rounding of the lifted poses X (r x (d+1) n) in the frame of the lifted pose `anchor` (r x (d+1); None =
+    pose 0 of X, PGOAgent::getTrajectoryInLocalFrame): d x (d+1) n, [R_j | t_j] per pose."""
+    r = X.shape[0]
+    n = X.shape[1] // (d + 1)
+    x, xp = _f64(to_dev_layout(X))
+    ap = None
+    if anchor is not None:
+        a, ap = _f64(to_dev_layout(anchor))
+    o = np.empty(n * d * (d + 1))
+    _check(lib().dpgo_hip_round_se(r, d, n, xp, ap, o.ctypes.data_as(_dp)))
+    return from_dev_layout(o, d)
+
+
+def round_se_dev(r, d, n, X_dev: int, anchor_dev: int | None, T_dev: int, stream_ptr: int | None = None):
+    """round_se on device pointers, queued on `stream_ptr` (None = the null stream) without synchronisation."""
+    _check(lib().dpgo_hip_round_se_dev(int(r), int(d), int(n), C.c_void_p(X_dev), C.c_void_p(anchor_dev or 0),
+                                       C.c_void_p(T_dev), C.c_void_p(stream_ptr or 0)))
+
+
 # ----------------------------------------------------------------------------------------
 # Pose graphs + multi-agent RBCD engine (include/dpgo_rbcd.h)
 # ----------------------------------------------------------------------------------------
@@ -547,6 +570,10 @@ _SIGS2 = [
     ("dpgo_rbcd_exchange_counts", [C.c_void_p, _lp, _lp], C.c_int),
     ("dpgo_rbcd_set_X", [C.c_void_p, _dp], C.c_int),
     ("dpgo_rbcd_get_X", [C.c_void_p, _dp], C.c_int),
+    ("dpgo_rbcd_get_anchor", [C.c_void_p, C.c_int, _dp, _ip], C.c_int),
+    ("dpgo_rbcd_get_trajectory", [C.c_void_p, _dp, _dp], C.c_int),
+    ("dpgo_rbcd_get_weights", [C.c_void_p, _dp], C.c_int),
+    ("dpgo_rbcd_weight_owner", [C.c_void_p, C.c_int, _ip, _ip], C.c_int),
     ("dpgo_rbcd_pre_exchange", [C.c_void_p, C.c_int], C.c_int),
     ("dpgo_rbcd_pack", [C.c_void_p, C.c_void_p], C.c_int),
     ("dpgo_rbcd_update", [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(OptResult)], C.c_int),
@@ -780,6 +807,17 @@ def exchange_plan_color(graph: "Graph", agent_of_pose, agent_rank, color, rank, 
     return ([sp_[so[p]:so[p + 1]] for p in range(world)], [rp_[ro[p]:ro[p + 1]] for p in range(world)])
 
 
+def weight_owner(graph: "Graph", agent_of_pose, num_agents):
+    """Host-only: per edge the agent whose weight Rbcd.weights_into reports (-1 = odometry, weight 1; a shared loop
+    closure: the lower-ID agent)."""
+    aop, ap = _i32(agent_of_pose)
+    if len(aop) != graph.n:
+        raise ValueError(f"agent_of_pose has {len(aop)} entries, the graph has {graph.n} poses")
+    out = np.empty(graph.m, np.int32)
+    _check(lib().dpgo_rbcd_weight_owner(graph.h, int(num_agents), ap, out.ctypes.data_as(_ip)))
+    return out
+
+
 def lifting_matrix(d, r, seed=2):
     """Repo-defined lifting matrix YLift in St(d, r) (replaces ROPTLIB's RNG)."""
     M = np.random.default_rng(seed).standard_normal((r, d))
@@ -856,6 +894,37 @@ class Rbcd:
         if Xflat.size < need:
             raise ValueError(f"X buffer holds {Xflat.size} doubles, the graph needs {need}")
         _check(lib().dpgo_rbcd_get_X(self.h, Xflat.ctypes.data_as(_dp)))
+
+    def anchor(self, pose=0):
+        """The lifted pose of global pose `pose` (r x (d+1)) if this rank owns it, else None."""
+        r, b = self.params.r, self.graph.d + 1
+        a = np.empty(r * b)
+        owned = C.c_int()
+        _check(lib().dpgo_rbcd_get_anchor(self.h, int(pose), a.ctypes.data_as(_dp), C.byref(owned)))
+        return from_dev_layout(a, r) if owned.value else None
+
+    def trajectory_into(self, T_flat, anchor=None):
+        """getTrajectoryInGlobalFrame of every owned agent in the frame of `anchor` (r x (d+1); None = global pose 0,
+        which this rank must own), rounded on the device: written at the owned poses of a global flat d x (d+1) n
+        column-major host array (from_dev_layout(T_flat, d) is the d x (d+1) n matrix)."""
+        assert T_flat.dtype == np.float64 and T_flat.flags.c_contiguous
+        need = self.graph.n * (self.graph.d + 1) * self.graph.d
+        if T_flat.size < need:
+            raise ValueError(f"T buffer holds {T_flat.size} doubles, the graph needs {need}")
+        ap = None
+        if anchor is not None:
+            a, ap = _f64(to_dev_layout(anchor))
+            if a.size != self.params.r * (self.graph.d + 1):
+                raise ValueError("anchor must be r x (d+1)")
+        _check(lib().dpgo_rbcd_get_trajectory(self.h, ap, T_flat.ctypes.data_as(_dp)))
+
+    def weights_into(self, w):
+        """Current weight of every measurement this rank is responsible for (weight_owner's agent lives here), at
+        its index in the graph's edge order; other entries untouched."""
+        assert w.dtype == np.float64 and w.flags.c_contiguous
+        if w.size < self.graph.m:
+            raise ValueError(f"w holds {w.size} doubles, the graph has {self.graph.m} edges")
+        _check(lib().dpgo_rbcd_get_weights(self.h, w.ctypes.data_as(_dp)))
 
     def reset_stream(self):
         _check(lib().dpgo_rbcd_reset_stream(self.h))

@@ -165,6 +165,16 @@ int dpgo_hip_retract_qf(int r, int d, int n, const double* X, const double* V, d
                         double* out);
 /* LiftedSEManifold::project (src/manifold/LiftedSEManifold.cpp:34-45) */
 int dpgo_hip_project_polar(int r, int d, int n, const double* in, double* out);
+/* T (d x (d+1) n, column-major) = SE(d) rounding of X (r x (d+1) n) in the frame of `anchor`
+ * (r x (d+1), column-major; NULL = pose 0 of X, i.e. getTrajectoryInLocalFrame): per pose
+ * R_j = projectToRotationGroup(Y_a^T Y_j), t_j = Y_a^T p_j - Y_a^T p_a
+ * (PGOAgent::getTrajectoryInGlobalFrame, src/PGOAgent.cpp:500-519).  DPGO_HIP_EINVAL for an unsupported
+ * (r, d), n <= 0, or null X or T. */
+int dpgo_hip_round_se(int r, int d, int n, const double* X, const double* anchor, double* T);
+/* the same on device pointers, queued on `stream` (hipStream_t or NULL), no synchronisation; T_dev must not
+ * overlap X_dev */
+int dpgo_hip_round_se_dev(int r, int d, long long n, const double* X_dev, const double* anchor_dev,
+                          double* T_dev, void* stream);
 
 /* ---- optimisation (QuadraticOptimizer::optimize, src/QuadraticOptimizer.cpp:34-149) -----*/
 /* Runs every agent of the handle; results[num_agents].  agent_enabled (optional, device or

@@ -151,6 +151,27 @@ int dpgo_rbcd_exchange_counts(dpgo_rbcd e, long long* send_counts, long long* re
 int dpgo_rbcd_set_X(dpgo_rbcd e, const double* X_global);
 /* write the owned poses into a global host array (other poses untouched) */
 int dpgo_rbcd_get_X(dpgo_rbcd e, double* X_global);
+/* ---- solution readout: SE(d) trajectory and loop-closure weights ---------------------------
+ * lifted pose of global pose `pose` (r x (d+1), column-major) if this rank owns it: *owned = 1 and
+ * anchor written; else *owned = 0 and anchor untouched.  Synchronises.  (PGOAgent::setGlobalAnchor takes
+ * this pose; with several ranks the caller broadcasts it from the rank that owns it.) */
+int dpgo_rbcd_get_anchor(dpgo_rbcd e, int pose, double* anchor, int* owned);
+/* getTrajectoryInGlobalFrame (src/PGOAgent.cpp:500-519) of every owned agent in the frame of `anchor` (NULL =
+ * global pose 0, which this rank must own, else EINVAL): rounded on the device from the engine's X
+ * (dpgo_hip_round_se_dev on the engine's stream, after whatever is queued there), written at the owned poses
+ * of a global d x (d+1) n column-major host array (other poses untouched, as get_X).  Only the rounded
+ * poses cross to the host.  Synchronises. */
+int dpgo_rbcd_get_trajectory(dpgo_rbcd e, const double* anchor, double* T_global);
+/* current weight of every measurement this rank is responsible for, at its index in the graph's
+ * edge order (w[m]; entries of other ranks' edges untouched).  Responsible = dpgo_rbcd_weight_owner's agent
+ * lives on this rank; odometry (owner -1) is written by the rank of its agent, always 1.  With
+ * robust_cost L2 every written entry is exactly 1. */
+int dpgo_rbcd_get_weights(dpgo_rbcd e, double* w);
+/* host-only: the agent whose weight dpgo_rbcd_get_weights reports per edge (owner[m]); -1 = odometry
+ * (both poses in one agent at consecutive local indices), never reweighted, weight 1.  A private loop
+ * closure: its agent.  A shared loop closure: the lower-ID agent of the two -- the only copy
+ * PGOAgent::updateLoopClosuresWeights ever updates (src/PGOAgent.cpp:1201-1235); the other copy stays 1. */
+int dpgo_rbcd_weight_owner(dpgo_graph g, int num_agents, const int* agent_of_pose, int* owner);
 /* Phase 1 of iteration with selected colour c: every non-selected agent runs iterate(false).  Any colour order:
  * a robust cost's reweighting (src/PGOAgent.cpp:1174-1244) reads the agent's own X and, for shared loop closures,
  * its neighborPoseDict -- the neighbour poses it received when it was last selected (the engine snapshots them in
