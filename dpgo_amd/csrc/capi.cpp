@@ -798,7 +798,7 @@ int sync_chol(dpgo_hip_problem h) {
   // ---- upload
   // every upload is ordered on h->stream (the handle's stream is non-blocking: a copy on the null stream is not
   // ordered before the sweeps and factor kernels queued after it); the host vectors live until the stream
-  // synchronisation at the end of this function (host path) or in device_factor
+  // synchronisation at the end of this function (both paths: device_factor itself never waits)
   auto up = [&](auto& d, const auto& v) -> int {
     using T = typename std::decay_t<decltype(v)>::value_type;
     HIP_TRY(d.ensure(std::max<size_t>(v.size(), 1)));
@@ -1098,6 +1098,9 @@ int sync_chol(dpgo_hip_problem h) {
   HIP_TRY(h->fac_not_pd.ensure(K));
   for (int q = 0; q < 2; ++q) HIP_TRY(h->fac_F[q].ensure(std::max<long>(level_size[q], 1)));
   h->sn_sym_ready = true;
+  // the uploaded host tables die with this frame: an asynchronous copy from pageable memory need not have read its
+  // source when the call returns.  Only after a symbolic rebuild; refactorisations (sn_sym_ready) never wait.
+  HIP_TRY(hipStreamSynchronize(h->stream));
   return device_factor(h);
 }
 
