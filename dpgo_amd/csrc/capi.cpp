@@ -2610,6 +2610,128 @@ int dpgo_hip_round_se(int r, int d, int n, const double* X, const double* anchor
   return download(T, t.p, db * n, s);
 }
 
+// ----------------------------------------------------------------------- rank staircase
+namespace {
+int check_lift(int r, int d, const void* X, const void* out, long long n) {
+  if ((d != 2 && d != 3) || r < d || !dpgo::supported_rb(r, d + 1))
+    return fail(DPGO_HIP_EINVAL, "lift_escape: unsupported (r, d)");
+  if (!dpgo::supported_rb(r + 1, d + 1)) return fail(DPGO_HIP_EINVAL, "lift_escape: rank r + 1 is not compiled");
+  if (n <= 0) return fail(DPGO_HIP_EINVAL, "lift_escape: need n >= 1 poses");
+  if (!X || !out) return fail(DPGO_HIP_EINVAL, "lift_escape: null X or X_out");
+  return DPGO_HIP_OK;
+}
+}  // namespace
+
+int dpgo_hip_lift_escape_dev(int r, int d, long long n, const double* X_dev, const double* v_dev, double alpha,
+                             double* X_out_dev, void* stream) {
+  DPGO_TRY(check_lift(r, d, X_dev, X_out_dev, n));
+  if (usable_devices() == 0) return fail(DPGO_HIP_ENODEV, "no gfx950 device available (no CPU fallback)");
+  HIP_TRY(dpgo::launch_lift_escape(r, d + 1, static_cast<long>(n), X_dev, v_dev, alpha, X_out_dev,
+                                   static_cast<hipStream_t>(stream)));
+  return DPGO_HIP_OK;
+}
+
+int dpgo_hip_lift_escape(int r, int d, int n, const double* X, const double* v, double alpha, double* X_out) {
+  DPGO_TRY(check_lift(r, d, X, X_out, n));
+  if (usable_devices() == 0) return fail(DPGO_HIP_ENODEV, "no gfx950 device available (no CPU fallback)");
+  const size_t b = static_cast<size_t>(d) + 1, rb = r * b, ob = (r + 1) * b;
+  dpgo::DevBuf<double> x, vv, o;
+  HIP_TRY(x.ensure(rb * n));
+  HIP_TRY(o.ensure(ob * n));
+  if (v) HIP_TRY(vv.ensure(b * n));
+  hipStream_t s = nullptr;
+  HIP_TRY(hipMemcpyAsync(x.p, X, sizeof(double) * rb * n, hipMemcpyHostToDevice, s));
+  if (v) HIP_TRY(hipMemcpyAsync(vv.p, v, sizeof(double) * b * n, hipMemcpyHostToDevice, s));
+  DPGO_TRY(dpgo_hip_lift_escape_dev(r, d, n, x.p, v ? vv.p : nullptr, alpha, o.p, s));
+  return download(X_out, o.p, ob * n, s);
+}
+
+int dpgo_hip_escape_direction(int r, int d, int n, const double* eigvec, double* v) {
+  if (r < 1 || (d != 2 && d != 3) || n <= 0 || !eigvec || !v)
+    return fail(DPGO_HIP_EINVAL, "bad escape direction arguments");
+  const size_t len = (static_cast<size_t>(d) + 1) * n;
+  int best = -1;
+  double best_sq = 0.0;
+  for (int a = 0; a < r; ++a) {
+    double sq = 0.0;
+    for (size_t c = 0; c < len; ++c) sq += eigvec[c * r + a] * eigvec[c * r + a];
+    if (sq > best_sq) {
+      best_sq = sq;
+      best = a;
+    }
+  }
+  if (best < 0 || !std::isfinite(best_sq)) return fail(DPGO_HIP_EINVAL, "escape direction: no non-zero finite row");
+  const double inv = 1.0 / std::sqrt(best_sq);
+  for (size_t c = 0; c < len; ++c) v[c] = eigvec[c * r + best] * inv;
+  return DPGO_HIP_OK;
+}
+
+void dpgo_hip_default_escape_params(dpgo_escape_params* p) {
+  if (!p) return;
+  p->alpha0 = 1.0;
+  p->decrease = 0.25;
+  p->min_gradnorm = 0.0;
+  p->max_halvings = 30;
+}
+
+int dpgo_hip_escape(dpgo_hip_problem h, const double* X, const double* v, double lambda_min,
+                    const dpgo_escape_params* params, double* X_out, dpgo_escape_info* info) {
+  DPGO_TRY(check_handle(h));
+  if (!X || !v || !X_out || !info) return fail(DPGO_HIP_EINVAL, "escape: null argument");
+  if (h->K != 1) return fail(DPGO_HIP_EINVAL, "escape: single-agent handles only");
+  const int d = h->d, r = h->r - 1;
+  if (r < d) return fail(DPGO_HIP_EINVAL, "escape: the handle must hold rank r + 1 > d");
+  if (!(lambda_min < 0.0)) return fail(DPGO_HIP_EINVAL, "escape: lambda_min must be negative");
+  dpgo_escape_params p;
+  dpgo_hip_default_escape_params(&p);
+  if (params) p = *params;
+  if (!(p.alpha0 > 0.0) || !(p.decrease > 0.0) || p.max_halvings < 0 || !(p.min_gradnorm >= 0.0))
+    return fail(DPGO_HIP_EINVAL, "escape: bad parameters");
+  DPGO_TRY(check_lift(r, d, X, X_out, h->N));
+  DPGO_TRY(ready(h));
+  DPGO_TRY(ensure_work(h));
+  const size_t b = h->b, n = static_cast<size_t>(h->N);
+  dpgo::DevBuf<double> x, vv;
+  HIP_TRY(x.ensure(n * r * b));
+  HIP_TRY(vv.ensure(n * b));
+  DPGO_TRY(upload(x.p, X, n * r * b, h->stream));
+  DPGO_TRY(upload(vv.p, v, n * b, h->stream));
+  // f of the lifted point at h->x2 through the each-edge-once pass (QuadraticProblem::f)
+  auto f_at_x2 = [&](double* f) -> int {
+    DPGO_TRY(eval_at(h, h->x2.p, nullptr, nullptr, h->pa.p, dpgo::FLAG_NONE, dpgo::MODE_F));
+    DPGO_TRY(finalize(h, dpgo::OP_SUM, h->pa.p, 2, nullptr, 0));
+    DPGO_TRY(download_sums(h));
+    *f = h->h_sums[0];
+    return DPGO_HIP_OK;
+  };
+  auto lift_to_x2 = [&](const double* dir, double alpha) -> int {
+    HIP_TRY(dpgo::launch_lift_escape(r, h->b, h->N, x.p, dir, alpha, h->x2.p, h->stream));
+    return DPGO_HIP_OK;
+  };
+  std::memset(info, 0, sizeof(*info));
+  DPGO_TRY(lift_to_x2(nullptr, 0.0));
+  DPGO_TRY(f_at_x2(&info->f_before));
+  info->f_after = info->f_before;
+  bool passed = false;
+  double alpha = p.alpha0;
+  for (int k = 0; k <= p.max_halvings && !passed; ++k, alpha *= 0.5) {
+    DPGO_TRY(lift_to_x2(vv.p, alpha));
+    DPGO_TRY(f_at_x2(&info->f_after));
+    info->trials = k + 1;
+    info->alpha = alpha;
+    passed = info->f_after <= info->f_before + p.decrease * alpha * alpha * lambda_min;
+  }
+  if (passed) {  // |RieGrad(X+)| once, by the EVAL sweep of dpgo_hip_riegrad_dev
+    DPGO_TRY(eval_at(h, h->x2.p, h->tA.p, h->S.p, h->pa.p, dpgo::FLAG_NONE));
+    DPGO_TRY(finalize(h, dpgo::OP_SUM, h->pa.p, 2, nullptr, 0));
+    DPGO_TRY(download_sums(h));
+    info->gradnorm_after = std::sqrt(h->h_sums[1]);
+    info->accepted = info->gradnorm_after >= p.min_gradnorm ? 1 : 0;
+  }
+  if (!info->accepted) DPGO_TRY(lift_to_x2(nullptr, 0.0));
+  return download(X_out, h->x2.p, h->vec_len(), h->stream);
+}
+
 // ----------------------------------------------------------------------- certification
 }  // extern "C"
 

@@ -633,3 +633,27 @@ int dpgo_graph_certify_ex(dpgo_graph g, int r, const double* X, int max_iters, i
   if (T_rounded) std::memcpy(T_rounded, T.data(), sizeof(double) * T.size());
   return DPGO_HIP_OK;
 }
+
+// The rank staircase's step on the whole graph (build-defined, next to dpgo_graph_certify_ex): the central
+// unit-weight edge-stream handle at rank r + 1, the direction from the certificate's Ritz matrix (or a plain
+// eigenvector, vec_rows = 1), and dpgo_hip_escape's line search on it.  X_out: (r + 1) x (d+1) n, column-major.
+int dpgo_graph_escape(dpgo_graph g, int r, const double* X, const double* eigvec_or_v, int vec_rows,
+                      double lambda_min, const dpgo_escape_params* params, double* X_out, dpgo_escape_info* info) {
+  if (!g || !X || !eigvec_or_v || !X_out || !info || r < g->d || vec_rows < 1)
+    return fail(DPGO_HIP_EINVAL, "bad escape arguments");
+  if (r >= 8) return fail(DPGO_HIP_EINVAL, "escape: rank r + 1 is not compiled");
+  if (!(lambda_min < 0.0)) return fail(DPGO_HIP_EINVAL, "escape: lambda_min must be negative");
+  const int d = g->d, n = g->n, m = static_cast<int>(g->p1.size());
+  std::vector<double> v(static_cast<size_t>(n) * (d + 1));
+  DPGO_TRY(dpgo_hip_escape_direction(vec_rows, d, n, eigvec_or_v, v.data()));
+  dpgo_hip_problem h = nullptr;
+  DPGO_TRY(dpgo_hip_problem_create(n, d, r + 1, &h));
+  struct Guard {
+    dpgo_hip_problem h;
+    ~Guard() { dpgo_hip_problem_destroy(h); }
+  } guard{h};
+  const std::vector<double> w(static_cast<size_t>(m), 1.0);
+  DPGO_TRY(dpgo_hip_set_Q_edges(h, 0, m, g->p1.data(), g->p2.data(), g->R.data(), g->t.data(), g->kappa.data(),
+                                g->tau.data(), w.data()));
+  return dpgo_hip_escape(h, X, v.data(), lambda_min, params, X_out, info);
+}

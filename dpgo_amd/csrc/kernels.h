@@ -450,6 +450,12 @@ hipError_t launch_polar_comb(int r, int b, const LaunchCtx& c, const double* A, 
 // No tile set: any n >= 1; T must not overlap X.
 hipError_t launch_round_se(int r, int b, long n, const double* X, const double* anchor, double* T,
                            hipStream_t stream);
+// Rank staircase: out ((r + 1) x b per pose) = Retr_[X; 0](alpha [0; v^T]) of the n lifted poses X (r x b per pose),
+// v the (b n)-vector of the direction (pose j's slice v[b j .. b j + b)): out_j = [qf([Y_j; alpha v_Y^T]) |
+// (p_j; alpha v_p)] with k_retract's qf.  v null: the plain lift [X; 0], bitwise.  No tile set: any n >= 1; rank
+// r + 1 must be compiled (hipErrorInvalidValue for r = 8); out must not overlap X.
+hipError_t launch_lift_escape(int r, int b, long n, const double* X, const double* v, double alpha, double* out,
+                              hipStream_t stream);
 // PGOAgent::computeConvergedLoopClosureRatio (src/PGOAgent.cpp:1247-1289): per agent a, the share of
 // its loop closures idx[off[a] .. off[a+1]) whose weight w[] is exactly 1 or 0 (0/0 = NaN, as there)
 hipError_t launch_conv_ratio(int num_agents, const int* off, const int* idx, const double* w, double* ratio,

@@ -2711,6 +2711,111 @@ __global__ __launch_bounds__(64) void k_round_se(long n, const double* __restric
   }
 }
 
+// Rank staircase: lift the n poses X (R x B each) to rank R + 1 and move along the certificate's negative-curvature
+// direction, X+ = Retr_[X; 0](alpha [0; v^T]) (build-defined; SE-Sync's saddle escape):
+// per pose j with v_j = (v_Y (D), v_p) the pose's slice of the (D+1) n vector v,
+//   out_j = [qf([Y_j; alpha v_Y^T]) | (p_j; alpha v_p)],   (R + 1) x B column-major,
+// qf being k_retract's (qf_inplace).  v == nullptr is the plain lift [X; 0]: a relayout, no arithmetic on X's entries.
+// k_round_se's shape: block k takes poses [64 k, 64 k + 64); the R B-wide span and the B-wide span of v stream
+// through LDS coalesced (16-byte chunks where the span width is even, the block full and the span aligned, 8-byte
+// otherwise), thread t works on pose t, and the (R + 1) B-wide result streams out of the same LDS.  Row strides are
+// the span widths made odd (conflict-free b64 reads), at most (R + 1) B + 1 doubles.
+template <int R, int B>
+__global__ __launch_bounds__(64) void k_lift_escape(long n, const double* __restrict__ X,
+                                                    const double* __restrict__ v, double alpha,
+                                                    double* __restrict__ out) {
+  constexpr int D = B - 1;
+  constexpr int PW = R * B, PS = PW | 1;
+  constexpr int OW = (R + 1) * B, OS = OW | 1;
+  constexpr int VS = B | 1;
+  static_assert(PS <= OS, "the lifted poses reuse the staged span's LDS");
+  __shared__ double sm[64 * OS];
+  __shared__ double sv[64 * VS];
+  const int t = static_cast<int>(threadIdx.x);
+  const long first = static_cast<long>(blockIdx.x) * 64;
+  if (first >= n) return;
+  const int count = n - first < 64 ? static_cast<int>(n - first) : 64;
+  const double* src = X + first * PW;
+  double* dst = out + first * OW;
+  const bool full = count == 64;
+  if (PW % 2 == 0 && full && (reinterpret_cast<unsigned long>(src) & 15) == 0) {
+    constexpr int NV = PW / 2;  // 16-byte chunks per lane (PW even: a chunk never straddles two poses)
+    const double2* S2 = reinterpret_cast<const double2*>(src);
+    double2 w[NV];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) w[i] = S2[t + 64 * i];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int x = 2 * (t + 64 * i);
+      double* q = sm + (x / PW) * PS + x % PW;
+      q[0] = w[i].x;
+      q[1] = w[i].y;
+    }
+  } else {
+    const int total = count * PW;
+    for (int x = t; x < total; x += 64) sm[(x / PW) * PS + x % PW] = src[x];
+  }
+  if (v != nullptr) {
+    const double* vsrc = v + first * B;
+    if (B % 2 == 0 && full && (reinterpret_cast<unsigned long>(vsrc) & 15) == 0) {
+      constexpr int NB = B / 2;
+      const double2* V2 = reinterpret_cast<const double2*>(vsrc);
+      double2 w[NB];
+#pragma unroll
+      for (int i = 0; i < NB; ++i) w[i] = V2[t + 64 * i];
+#pragma unroll
+      for (int i = 0; i < NB; ++i) {
+        const int x = 2 * (t + 64 * i);
+        double* q = sv + (x / B) * VS + x % B;
+        q[0] = w[i].x;
+        q[1] = w[i].y;
+      }
+    } else {
+      const int total_v = count * B;
+      for (int x = t; x < total_v; x += 64) sv[(x / B) * VS + x % B] = vsrc[x];
+    }
+  }
+  __syncthreads();
+  const bool own = t < count;
+  double M[R + 1][B];
+  if (own) {
+    const double* ps = sm + t * PS;
+#pragma unroll
+    for (int c = 0; c < B; ++c) {
+#pragma unroll
+      for (int a = 0; a < R; ++a) M[a][c] = ps[c * R + a];
+      M[R][c] = 0.0;
+    }
+    if (v != nullptr) {  // block-uniform
+#pragma unroll
+      for (int c = 0; c < B; ++c) M[R][c] = alpha * sv[t * VS + c];
+      qf_inplace<R + 1, D>(M);
+    }
+  }
+  __syncthreads();  // every pose of the span is in registers: its LDS now takes the lifted poses
+  if (own) {
+    double* po = sm + t * OS;
+#pragma unroll
+    for (int c = 0; c < B; ++c)
+#pragma unroll
+      for (int a = 0; a < R + 1; ++a) po[c * (R + 1) + a] = M[a][c];
+  }
+  __syncthreads();
+  if (OW % 2 == 0 && full && (reinterpret_cast<unsigned long>(dst) & 15) == 0) {
+    constexpr int NO = OW / 2;
+    double2* O2 = reinterpret_cast<double2*>(dst);
+#pragma unroll
+    for (int i = 0; i < NO; ++i) {
+      const int x = 2 * (t + 64 * i);
+      const double* q = sm + (x / OW) * OS + x % OW;
+      O2[t + 64 * i] = make_double2(q[0], q[1]);
+    }
+  } else {
+    const int total_out = count * OW;
+    for (int x = t; x < total_out; x += 64) dst[x] = sm[(x / OW) * OS + x % OW];
+  }
+}
+
 // Nesterov updateV deferred into the colour's next combination pass (one pass instead of two):
 //   V' = project(V + gv (X - Yv))   (updateV, src/PGOAgent.cpp:1086-1091, of the agent's last update)
 //   out = project(sa X + sb V')     (updateY / the iterate(false) step, :1077-1084, of the next iteration)
@@ -5035,6 +5140,16 @@ hipError_t launch_round_se(int r, int b, long n, const double* X, const double* 
   const dim3 grid(static_cast<unsigned>(blocks));
   const double* A = anchor != nullptr ? anchor : X;  // the local frame: pose 0 of X
   DPGO_DISPATCH(r, b, (k_round_se<R, B><<<grid, 64, 0, stream>>>(n, X, A, T)));
+  return hipGetLastError();
+}
+
+hipError_t launch_lift_escape(int r, int b, long n, const double* X, const double* v, double alpha, double* out,
+                              hipStream_t stream) {
+  if (n <= 0 || X == nullptr || out == nullptr || !supported_rb(r + 1, b)) return hipErrorInvalidValue;
+  const long blocks = (n + 63) / 64;
+  if (blocks > 0x7fffffffL) return hipErrorInvalidValue;
+  const dim3 grid(static_cast<unsigned>(blocks));
+  DPGO_DISPATCH(r, b, (k_lift_escape<R, B><<<grid, 64, 0, stream>>>(n, X, v, alpha, out)));
   return hipGetLastError();
 }
 

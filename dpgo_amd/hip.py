@@ -42,6 +42,21 @@ class OptResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class EscapeParams(C.Structure):
+    """dpgo_escape_params (include/dpgo_hip.h)."""
+    _fields_ = [("alpha0", C.c_double), ("decrease", C.c_double), ("min_gradnorm", C.c_double),
+                ("max_halvings", C.c_int)]
+
+
+class EscapeInfo(C.Structure):
+    """dpgo_escape_info (include/dpgo_hip.h)."""
+    _fields_ = [("accepted", C.c_int), ("trials", C.c_int), ("alpha", C.c_double), ("f_before", C.c_double),
+                ("f_after", C.c_double), ("gradnorm_after", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class DPGOHipError(RuntimeError):
     pass
 
@@ -77,6 +92,13 @@ _SIGS = [
     ("dpgo_hip_project_polar", [C.c_int, C.c_int, C.c_int, _dp, _dp], C.c_int),
     ("dpgo_hip_round_se", [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp], C.c_int),
     ("dpgo_hip_round_se_dev", [C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+     C.c_int),
+    ("dpgo_hip_lift_escape", [C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_double, _dp], C.c_int),
+    ("dpgo_hip_lift_escape_dev", [C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p,
+                                  C.c_void_p], C.c_int),
+    ("dpgo_hip_escape_direction", [C.c_int, C.c_int, C.c_int, _dp, _dp], C.c_int),
+    ("dpgo_hip_default_escape_params", [C.POINTER(EscapeParams)], None),
+    ("dpgo_hip_escape", [C.c_void_p, _dp, _dp, C.c_double, C.POINTER(EscapeParams), _dp, C.POINTER(EscapeInfo)],
      C.c_int),
     ("dpgo_hip_optimize", [C.c_void_p, C.POINTER(OptParams), _dp, _dp, C.POINTER(OptResult)], C.c_int),
     ("dpgo_hip_f_dev", [C.c_void_p, C.c_void_p, _dp], C.c_int),
@@ -405,6 +427,23 @@ class Problem:
         self.last_certificate = info.as_dict()
         return lam.value, info.residual, info.iters, (from_dev_layout(v, self.r) if v is not None else None)
 
+    def escape(self, X, v, lambda_min, params: "EscapeParams | None" = None):
+        """The rank staircase's escape with its line search on this handle (single agent, rank r + 1, Q set): X
+        (r x (d+1) n) a critical point of rank r = self.r - 1, v the unit eigenvector of lambda_min(S(X)) < 0.
+        Returns (X_out (r+1) x (d+1) n, info dict); not accepted: X_out = [X; 0] (dpgo_hip_escape)."""
+        X = np.asarray(X, dtype=np.float64)
+        if X.shape != (self.r - 1, self.b * self.N):
+            raise DPGOHipError(f"escape: X must be {self.r - 1} x {self.b * self.N} for this rank-{self.r} handle")
+        x, xp = _f64(to_dev_layout(X))
+        vv, vp = _f64(np.asarray(v, dtype=np.float64).ravel())
+        if vv.size != self.b * self.N:
+            raise DPGOHipError("escape: v must have (d+1) n entries")
+        o, op = self._out()
+        info = EscapeInfo()
+        _check(lib().dpgo_hip_escape(self.h, xp, vp, float(lambda_min), C.byref(params) if params else None, op,
+                                     C.byref(info)))
+        return from_dev_layout(o, self.r), info.as_dict()
+
     def spmm_bytes(self) -> float:
         return float(lib().dpgo_hip_spmm_bytes(self.h))
 
@@ -511,6 +550,48 @@ def round_se_dev(r, d, n, X_dev: int, anchor_dev: int | None, T_dev: int, stream
                                        C.c_void_p(T_dev), C.c_void_p(stream_ptr or 0)))
 
 
+def escape_params(**kw) -> EscapeParams:
+    p = EscapeParams()
+    lib().dpgo_hip_default_escape_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def lift_escape(X, d, v=None, alpha=1.0):
+    """Retr_[X; 0](alpha [0; v^T]) of the lifted poses X (r x (d+1) n) along the (d+1) n vector v, at rank r + 1:
+    per pose [qf([Y_j; alpha v_Y^T]) | (p_j; alpha v_p)].  v None: the plain lift [X; 0].  (r+1) x (d+1) n."""
+    r = X.shape[0]
+    n = X.shape[1] // (d + 1)
+    x, xp = _f64(to_dev_layout(X))
+    vp = None
+    if v is not None:
+        vv, vp = _f64(np.asarray(v, dtype=np.float64).ravel())
+        if vv.size != (d + 1) * n:
+            raise DPGOHipError("lift_escape: v must have (d+1) n entries")
+    o = np.empty(n * (r + 1) * (d + 1))
+    _check(lib().dpgo_hip_lift_escape(r, d, n, xp, vp, float(alpha), o.ctypes.data_as(_dp)))
+    return from_dev_layout(o, r + 1)
+
+
+def lift_escape_dev(r, d, n, X_dev: int, v_dev: int | None, alpha, X_out_dev: int, stream_ptr: int | None = None):
+    """lift_escape on device pointers, queued on `stream_ptr` (None = the null stream) without synchronisation."""
+    _check(lib().dpgo_hip_lift_escape_dev(int(r), int(d), int(n), C.c_void_p(X_dev), C.c_void_p(v_dev or 0),
+                                          float(alpha), C.c_void_p(X_out_dev), C.c_void_p(stream_ptr or 0)))
+
+
+def escape_direction(vec, d):
+    """The unit escape direction ((d+1) n) from the certificate's Ritz matrix (r x (d+1) n: its row of largest
+    norm) or from a plain (d+1) n vector.  Host only."""
+    V = np.asarray(vec, dtype=np.float64)
+    V = V.reshape(1, -1) if V.ndim == 1 else V
+    r, n = V.shape[0], V.shape[1] // (d + 1)
+    x, xp = _f64(to_dev_layout(V))
+    out = np.empty(V.shape[1])
+    _check(lib().dpgo_hip_escape_direction(r, d, n, xp, out.ctypes.data_as(_dp)))
+    return out
+
+
 # ----------------------------------------------------------------------------------------
 # Pose graphs + multi-agent RBCD engine (include/dpgo_rbcd.h)
 # ----------------------------------------------------------------------------------------
@@ -554,6 +635,8 @@ _SIGS2 = [
      C.c_int),
     ("dpgo_graph_certify_ex", [C.c_void_p, C.c_int, _dp, C.c_int, C.c_int, C.c_int, C.c_double, _dp, _dp, _dp, _dp,
                                _dp, C.c_void_p], C.c_int),
+    ("dpgo_graph_escape", [C.c_void_p, C.c_int, _dp, _dp, C.c_int, C.c_double, C.POINTER(EscapeParams), _dp,
+                           C.POINTER(EscapeInfo)], C.c_int),
     ("dpgo_chordal_initialization_gpu", [C.c_int, C.c_int, C.c_int, _ip, _ip, _dp, _dp, _dp, _dp, C.c_double,
                                          C.c_int, _dp, _ip, _dp], C.c_int),
     ("dpgo_graph_chordal_init_gpu", [C.c_void_p, C.c_int, _dp, C.c_double, C.c_int, _dp, _ip, _dp], C.c_int),
@@ -743,6 +826,28 @@ class Graph:
         if V is not None:
             out["eigvec"] = V.reshape(-1, r).T if V.ndim == 1 else V  # r x (d+1) n
         return out
+
+    def escape(self, X, r, vec, lambda_min, params: "EscapeParams | None" = None):
+        """The rank staircase's step after certify() returned lambda_min < 0 at the critical point X (flat r x (d+1) n
+        column-major buffer, or the matrix): vec = certify's "eigvec" (r x (d+1) n) or a plain eigenvector
+        ((d+1) n).  Returns (X_out, flat (r+1) x (d+1) n column-major, ready for Rbcd.set_X at rank r + 1; info
+        dict(accepted, trials, alpha, f_before, f_after, gradnorm_after))."""
+        X = np.asarray(X, dtype=np.float64)
+        flat = np.ascontiguousarray(X.T).ravel() if X.ndim == 2 else np.ascontiguousarray(X).ravel()
+        bn = (self.d + 1) * self.n
+        if flat.size != r * bn:
+            raise DPGOHipError("X has the wrong size")
+        V = np.asarray(vec, dtype=np.float64)
+        V = V.reshape(1, -1) if V.ndim == 1 else V
+        if V.shape[1] != bn:
+            raise DPGOHipError("the direction must have (d+1) n columns")
+        vv, vp = _f64(to_dev_layout(V))
+        out = np.empty((r + 1) * bn)
+        info = EscapeInfo()
+        _check(lib().dpgo_graph_escape(self.h, int(r), flat.ctypes.data_as(_dp), vp, int(V.shape[0]),
+                                       float(lambda_min), C.byref(params) if params else None,
+                                       out.ctypes.data_as(_dp), C.byref(info)))
+        return out, info.as_dict()
 
     def grid_partition(self, agents_per_axis):
         out = np.empty(self.n, np.int32)

@@ -270,6 +270,51 @@ typedef struct {
 int dpgo_hip_certify_ex(dpgo_hip_problem h, const double* X, int max_iters, int basis_max, int flags, double tol,
                         double* lambda_min, double* eigvec, dpgo_cert_info* info);
 
+/* ---- rank staircase (SE-Sync / DC2-PGO's Riemannian staircase; not in the reference: pinned against the
+ * oracle's retract_qf and a numpy restatement) ------------------------------------------------------
+ * When the certificate fails at a critical point X of rank r (lambda_min(S(X)) < 0 with eigenvector v, a
+ * (d+1) n vector), [X; 0] is a saddle of the rank r + 1 problem and [0; v^T] a direction of negative curvature
+ * there: f(Retr_[X; 0](alpha [0; v^T])) = f(X) + 1/2 alpha^2 lambda_min + O(alpha^3) for unit v.
+ * dpgo_hip_lift_escape: X_out ((r+1) x (d+1) n) = Retr_[X; 0](alpha [0; v^T]) with the QF retraction of
+ * dpgo_hip_retract_qf, per pose [qf([Y_j; alpha v_Y^T]) | (p_j; alpha v_p)]; v NULL = the plain lift [X; 0]
+ * (bitwise X's entries and zeros).  One streaming kernel.  DPGO_HIP_EINVAL for an unsupported (r, d), r = 8
+ * (rank 9 is not compiled), n <= 0, or null X or X_out. */
+int dpgo_hip_lift_escape(int r, int d, int n, const double* X, const double* v, double alpha, double* X_out);
+/* the same on device pointers, queued on `stream` (hipStream_t or NULL), no synchronisation; X_out_dev must not
+ * overlap X_dev */
+int dpgo_hip_lift_escape_dev(int r, int d, long long n, const double* X_dev, const double* v_dev, double alpha,
+                             double* X_out_dev, void* stream);
+/* The escape direction from the certificate's Ritz matrix eigvec (r x (d+1) n, column-major, as dpgo_hip_certify*
+ * returns it: the operator acts row by row, so every non-zero row is an eigenvector of S): the row of largest
+ * 2-norm, normalised, into v ((d+1) n).  r = 1 takes a plain vector.  Host only, no device needed.
+ * DPGO_HIP_EINVAL if every row is zero. */
+int dpgo_hip_escape_direction(int r, int d, int n, const double* eigvec, double* v);
+typedef struct {
+  double alpha0;        /* first step length tried (1) */
+  double decrease;      /* accept when f(X+) <= f_before + decrease alpha^2 lambda_min (0.25: half the prediction) */
+  double min_gradnorm;  /* the escape is accepted only if |RieGrad(X+)| >= this (0): set it to the tolerance below
+                           which the solver that takes X+ returns its input unchanged */
+  int max_halvings;     /* alpha = alpha0 2^-k, k <= max_halvings (30) */
+} dpgo_escape_params;
+typedef struct {
+  int accepted;          /* 1: X_out = X+(alpha); 0: X_out = the plain lift [X; 0] */
+  int trials;            /* step lengths evaluated */
+  double alpha;          /* the last step length tried */
+  double f_before;       /* f([X; 0]) on h_next */
+  double f_after;        /* f(X+(alpha)) */
+  double gradnorm_after; /* |RieGrad(X+(alpha))| (0 when no step length passed the decrease test) */
+} dpgo_escape_info;
+void dpgo_hip_default_escape_params(dpgo_escape_params* p);
+/* The escape with its line search.  h_next: a single-agent handle at rank r + 1 with Q set (r = its rank - 1);
+ * X (r x (d+1) n) and the unit direction v ((d+1) n) are uploaded once, then per trial one dpgo_hip_lift_escape_dev
+ * and one f through the handle's X.Q path run on the device and only f comes back.  The first alpha = alpha0 2^-k,
+ * k <= max_halvings, with f(X+) <= f_before + decrease alpha^2 lambda_min is taken, |RieGrad(X+)| is evaluated
+ * once, and the escape is accepted iff it is >= min_gradnorm (the gradient shrinks with alpha: a smaller alpha
+ * cannot help).  Not accepted, or no alpha passed: X_out = [X; 0], info filled, DPGO_HIP_OK.  params NULL = the
+ * defaults.  DPGO_HIP_EINVAL for lambda_min >= 0, a batched handle, or a handle of rank <= d. */
+int dpgo_hip_escape(dpgo_hip_problem h_next, const double* X, const double* v, double lambda_min,
+                    const dpgo_escape_params* params, double* X_out, dpgo_escape_info* info);
+
 /* ---- measurement helpers ----------------------------------------------------------------*/
 /* Select a compiled kernel variant / host sequence for A/B timing (process-wide; every setting gives
  * results within the documented bars, most bitwise the default's).  key 0: BSR X.Q SpMM

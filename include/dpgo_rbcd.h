@@ -89,6 +89,14 @@ int dpgo_graph_certify(dpgo_graph g, int r, const double* X, int max_iters, doub
 int dpgo_graph_certify_ex(dpgo_graph g, int r, const double* X, int max_iters, int basis_max, int flags, double tol,
                           double* lambda_min, double* f_relax, double* f_rounded, double* T_rounded, double* eigvec,
                           dpgo_cert_info* info);
+/* The rank staircase's step for the whole graph, next to dpgo_graph_certify_ex: when that returned lambda_min < 0
+ * at a critical point X of rank r, X_out ((r+1) x (d+1) n, column-major) = dpgo_hip_escape on the central
+ * unit-weight edge-stream handle at rank r + 1, along dpgo_hip_escape_direction of eigvec_or_v (vec_rows x (d+1) n,
+ * column-major: the certificate's eigvec with vec_rows = r, or a plain eigenvector with vec_rows = 1).  X_out then
+ * starts a solver at rank r + 1 (dpgo_rbcd_set_X of an engine created with params.r = r + 1).  DPGO_HIP_EINVAL for
+ * r = 8, r < d, lambda_min >= 0 or a zero direction. */
+int dpgo_graph_escape(dpgo_graph g, int r, const double* X, const double* eigvec_or_v, int vec_rows,
+                      double lambda_min, const dpgo_escape_params* params, double* X_out, dpgo_escape_info* info);
 int dpgo_graph_grid_partition(dpgo_graph g, int agents_per_axis, int* agent_of_pose);
 
 /* ---- RBCD engine ----------------------------------------------------------------------------*/
