@@ -754,6 +754,14 @@ int dpgo_rbcd_create(dpgo_graph g, int num_agents, const int* agent_of_pose, con
     if (rc == DPGO_HIP_OK && gc->dict.ensure(std::max<size_t>(gn_pe.size(), 1) * e->rb()) != hipSuccess)
       rc = fail(DPGO_HIP_ENOMEM, "GNC neighbour dictionary");
     if (rc == DPGO_HIP_OK) rc = upload_vec(gc->w_prob, std::vector<double>(std::max<long>(prob_edges, 1), 1.0), e->stream);
+    // computeConvergedLoopClosureRatio runs in every iterate (:706-712), also before the first reweighting: at unit
+    // weights it is 1, and 0/0 = NaN for an agent without loop closures (which is then ready whatever the threshold)
+    if (rc == DPGO_HIP_OK && e->P.robust_cost == DPGO_ROBUST_GNC_TLS) {
+      auto* l = e->lc[c];
+      if (launch_conv_ratio(h->K, l->off.p, l->idx.p, gc->w_prob.p, l->ratio.p, e->stream) != hipSuccess)
+        rc = fail(DPGO_HIP_EDEVICE, "converged ratio");
+      l->valid = true;
+    }
     if (rc == DPGO_HIP_OK && hipStreamSynchronize(e->stream) != hipSuccess) rc = fail(DPGO_HIP_EDEVICE, "sync");
     if (rc != DPGO_HIP_OK) return bail(rc);
   }

@@ -994,8 +994,12 @@ class AgentParams:
     def __init__(self, d, r, num_robots=1, algorithm="RTR", acceleration=False,
                  restart_interval=30, robust="GNC_TLS", robust_opt_inner_iters=30,
                  robust_opt_min_convergence_ratio=0.8, rel_change_tol=5e-3,
-                 precon=PRECON_EXACT):
+                 precon=PRECON_EXACT, gnc_max_iters=100, gnc_barc=10.0, gnc_mu_step=1.4,
+                 gnc_init_mu=1e-4, huber=3.0, tls=10.0):
         self.d, self.r, self.num_robots = d, r, num_robots
+        # RobustCostParameters (include/DPGO/DPGO_robust.h), held by PGOAgentParameters
+        self.robust_params = dict(gnc_max_iters=gnc_max_iters, gnc_barc=gnc_barc, gnc_mu_step=gnc_mu_step,
+                                  gnc_init_mu=gnc_init_mu, huber=huber, tls=tls)
         self.algorithm = algorithm
         self.acceleration = acceleration
         self.restart_interval = restart_interval
@@ -1014,7 +1018,7 @@ class Agent:
         self.n = 1
         self.iteration = 0
         self.initialized = False
-        self.robust = RobustCost(params.robust)
+        self.robust = RobustCost(params.robust, **params.robust_params)
         self.neighbor_pose = {}
         self.neighbor_aux_pose = {}
         self.X = None
@@ -1388,11 +1392,15 @@ def greedy_colors(meas: Measurements, agent_of_pose, num_agents):
 
 def colour_rbcd(meas: Measurements, agent_of_pose, num_agents, X0, num_iters, r,
                 acceleration=False, robust="L2", precon=PRECON_BLOCK_JACOBI, trace=None,
-                robust_opt_inner_iters=30, agents_out=None, algorithm="RTR"):
+                robust_opt_inner_iters=30, agents_out=None, algorithm="RTR", on_iteration=None,
+                **agent_kw):
     """Colour-class RBCD schedule run with the PGOAgent restatement: at iteration t the agents of
     colour t mod C are selected; the others run iterate(false) first (their public X / aux Y are
     then delivered, as in examples/MultiRobotExample.cpp:181-213), then the selected agents run
-    iterate(true).  Returns the global X after num_iters iterations."""
+    iterate(true).  agent_kw goes to every AgentParams: the robust-cost parameters (gnc_max_iters, gnc_barc,
+    gnc_mu_step, gnc_init_mu, huber, tls) and the termination ones (robust_opt_min_convergence_ratio,
+    rel_change_tol).  on_iteration(it, agents) is called after every iteration.  Returns the global X after
+    num_iters iterations."""
     d = meas.d
     b = d + 1
     n = len(agent_of_pose)
@@ -1409,7 +1417,7 @@ def colour_rbcd(meas: Measurements, agent_of_pose, num_agents, X0, num_iters, r,
     for a in range(num_agents):
         ag = Agent(a, AgentParams(d, r, num_agents, acceleration=acceleration, robust=robust,
                                   precon=precon, robust_opt_inner_iters=robust_opt_inner_iters,
-                                  algorithm=algorithm))
+                                  algorithm=algorithm, **agent_kw))
         ag.set_pose_graph(*parts[a], n=int(counts[a]))
         cols = np.concatenate([np.arange(p * b, (p + 1) * b) for p in glob[a]])
         ag.set_X(X0[:, cols])
@@ -1437,6 +1445,8 @@ def colour_rbcd(meas: Measurements, agent_of_pose, num_agents, X0, num_iters, r,
                 ag.iterate(True, trace)  # RTR outer records of the update, then (it, agent, result)
                 if trace is not None:
                     trace.append((it, ag.id, ag.last_result))
+        if on_iteration is not None:
+            on_iteration(it, agents)
     X = np.zeros_like(X0)
     for a, ag in enumerate(agents):
         cols = np.concatenate([np.arange(p * b, (p + 1) * b) for p in glob[a]])

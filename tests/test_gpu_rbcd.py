@@ -111,7 +111,7 @@ def _grid_with_outliers(hip, k, seed, frac, rng_seed):
 
 
 @pytest.mark.parametrize("accel", [False, True])
-@pytest.mark.parametrize("robust", ["GNC_TLS", "TLS", "Huber"])
+@pytest.mark.parametrize("robust", ["GNC_TLS", "TLS", "Huber", "GM", "L1"])
 def test_robust_reweighting_matches_oracle(hip, accel, robust):
     """Robust costs (GNC_TLS is the reference default) through two reweightings
     (robust_opt_inner_iters = 3: iterations 2 and 5; src/PGOAgent.cpp:642-718, 1174-1244;
