@@ -2610,6 +2610,56 @@ int dpgo_hip_round_se(int r, int d, int n, const double* X, const double* anchor
   return download(T, t.p, db * n, s);
 }
 
+namespace {
+int check_frame_lift(int r, int d, long long n, const void* T, const void* YLift, const void* frames, int nf,
+                     const void* frame_of, const void* out) {
+  if ((d != 2 && d != 3) || r < d || !dpgo::supported_rb(r, d + 1))
+    return fail(DPGO_HIP_EINVAL, "frame_lift: unsupported (r, d)");
+  if (n <= 0) return fail(DPGO_HIP_EINVAL, "frame_lift: need n >= 1 poses");
+  if (!T || !YLift || !out) return fail(DPGO_HIP_EINVAL, "frame_lift: null T, YLift or X_out");
+  if ((frames == nullptr) != (frame_of == nullptr))
+    return fail(DPGO_HIP_EINVAL, "frame_lift: frames and frame_of go together (both or neither)");
+  if (frames && nf <= 0) return fail(DPGO_HIP_EINVAL, "frame_lift: need nf >= 1 frames");
+  return DPGO_HIP_OK;
+}
+}  // namespace
+
+int dpgo_hip_frame_lift_dev(int r, int d, long long n, const double* T_dev, const double* YLift,
+                            const double* frames_dev, int nf, const int* frame_of_dev, double* X_out_dev,
+                            void* stream) {
+  DPGO_TRY(check_frame_lift(r, d, n, T_dev, YLift, frames_dev, nf, frame_of_dev, X_out_dev));
+  if (usable_devices() == 0) return fail(DPGO_HIP_ENODEV, "no gfx950 device available (no CPU fallback)");
+  dpgo::FrameLiftY y{};
+  std::memcpy(y.v, YLift, sizeof(double) * r * d);
+  HIP_TRY(dpgo::launch_frame_lift(r, d + 1, static_cast<long>(n), T_dev, y, frames_dev, frame_of_dev, X_out_dev,
+                                  static_cast<hipStream_t>(stream)));
+  return DPGO_HIP_OK;
+}
+
+int dpgo_hip_frame_lift(int r, int d, int n, const double* T, const double* YLift, const double* frames, int nf,
+                        const int* frame_of, double* X_out) {
+  DPGO_TRY(check_frame_lift(r, d, n, T, YLift, frames, nf, frame_of, X_out));
+  if (frame_of)
+    for (int j = 0; j < n; ++j)
+      if (frame_of[j] < 0 || frame_of[j] >= nf) return fail(DPGO_HIP_EINVAL, "frame_lift: frame_of entry out of range");
+  if (usable_devices() == 0) return fail(DPGO_HIP_ENODEV, "no gfx950 device available (no CPU fallback)");
+  const size_t rb = static_cast<size_t>(r) * (d + 1), db = static_cast<size_t>(d) * (d + 1);
+  dpgo::DevBuf<double> t, f, o;
+  dpgo::DevBuf<int> fo;
+  HIP_TRY(t.ensure(db * n));
+  HIP_TRY(o.ensure(rb * n));
+  hipStream_t s = nullptr;
+  HIP_TRY(hipMemcpyAsync(t.p, T, sizeof(double) * db * n, hipMemcpyHostToDevice, s));
+  if (frames) {
+    HIP_TRY(f.ensure(db * nf));
+    HIP_TRY(fo.ensure(static_cast<size_t>(n)));
+    HIP_TRY(hipMemcpyAsync(f.p, frames, sizeof(double) * db * nf, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(fo.p, frame_of, sizeof(int) * static_cast<size_t>(n), hipMemcpyHostToDevice, s));
+  }
+  DPGO_TRY(dpgo_hip_frame_lift_dev(r, d, n, t.p, YLift, frames ? f.p : nullptr, nf, frames ? fo.p : nullptr, o.p, s));
+  return download(X_out, o.p, rb * n, s);
+}
+
 // ----------------------------------------------------------------------- rank staircase
 namespace {
 int check_lift(int r, int d, const void* X, const void* out, long long n) {

@@ -509,6 +509,58 @@ int dpgo_graph_distributed_init(dpgo_graph g, int num_agents, const int* agent_o
   return DPGO_HIP_OK;
 }
 
+int dpgo_robust_rotation_average(int d, int n, const double* R, const double* kappa, double threshold, int max_iters,
+                                 double mu_step, double* R_opt, double* weights, int* iters) {
+  if ((d != 2 && d != 3) || n <= 0 || !R || !R_opt || !weights)
+    return fail(DPGO_HIP_EINVAL, "bad robust rotation averaging arguments");
+  std::string err;
+  if (dpgo::robust_rotation_average(d, n, R, kappa, threshold, max_iters, mu_step, R_opt, weights, iters, err) != 0)
+    return fail(DPGO_HIP_EINVAL, err);
+  return DPGO_HIP_OK;
+}
+
+void dpgo_default_init_params(dpgo_init_params* p) {
+  if (!p) return;
+  p->local_init = DPGO_LOCAL_CHORDAL;
+  p->align = DPGO_ALIGN_L2;
+  p->max_rotation_error = 2 * std::sqrt(2.0) * std::sin(0.25);  // angular2ChordalSO3(0.5)
+  p->gnc_max_iters = 1000;
+  p->gnc_mu_step = 1.4;
+  p->use_gpu = 0;
+  p->rtol = 1e-12;
+  p->max_iters = 20000;
+}
+
+int dpgo_graph_distributed_init_ex(dpgo_graph g, int num_agents, const int* agent_of_pose,
+                                   const dpgo_init_params* params, double* T_local, double* frames, int* parent,
+                                   int* candidates, int* inliers, unsigned char* edge_inlier, int* iters,
+                                   double* relres) {
+  if (!g || !agent_of_pose || num_agents <= 0 || !T_local || !frames || !parent || !candidates || !inliers)
+    return fail(DPGO_HIP_EINVAL, "null argument");
+  dpgo_init_params P;
+  dpgo_default_init_params(&P);
+  if (params) P = *params;
+  if ((P.local_init != DPGO_LOCAL_CHORDAL && P.local_init != DPGO_LOCAL_ODOMETRY) ||
+      (P.align != DPGO_ALIGN_L2 && P.align != DPGO_ALIGN_ROBUST_TWO_STAGE))
+    return fail(DPGO_HIP_EINVAL, "unknown local_init or align");
+  for (int i = 0; i < g->n; ++i)
+    if (agent_of_pose[i] < 0 || agent_of_pose[i] >= num_agents) return fail(DPGO_HIP_EINVAL, "agent_of_pose out of range");
+  const bool gpu = P.use_gpu != 0 && P.local_init == DPGO_LOCAL_CHORDAL;  // only the chordal solves can use the device
+  P.use_gpu = gpu ? 1 : 0;
+  if (gpu && usable_devices() == 0) return fail(DPGO_HIP_ENODEV, "no gfx950 device available (no CPU fallback)");
+  if (gpu && (!(P.rtol > 0.0) || P.max_iters < 1)) return fail(DPGO_HIP_EINVAL, "bad PCG tolerance");
+  if (P.align == DPGO_ALIGN_ROBUST_TWO_STAGE &&
+      (!(P.max_rotation_error > 0.0) || P.gnc_max_iters < 0 || !(P.gnc_mu_step > 0.0)))
+    return fail(DPGO_HIP_EINVAL, "bad GNC parameters");
+  std::string err;
+  if (dpgo::distributed_initialization_ex(g->d, g->n, static_cast<int>(g->p1.size()), g->p1.data(), g->p2.data(),
+                                          g->R.data(), g->t.data(), g->kappa.data(), g->tau.data(), agent_of_pose,
+                                          num_agents, P, T_local, frames, parent, candidates, inliers, edge_inlier,
+                                          iters, relres, err) != 0)
+    return fail(gpu ? DPGO_HIP_EDEVICE : DPGO_HIP_EINVAL, err);
+  return DPGO_HIP_OK;
+}
+
 int dpgo_graph_chain_init(dpgo_graph g, int r, const double* YLift, double* X_out) {
   if (!g || !YLift || !X_out) return fail(DPGO_HIP_EINVAL, "null argument");
   const int d = g->d, b = d + 1, n = g->n;

@@ -46,6 +46,15 @@ int chordal_initialization_gpu(int d, int n, int m, const int* p1, const int* p2
 // projectToRotationGroup of a d x d row-major matrix (init.cpp)
 void project_to_rotation(int d, const double* M, double* out);
 
+// robustSingleRotationAveraging and the multi-robot initialisation as local trajectories + frames
+// (dpgo_robust_rotation_average, dpgo_graph_distributed_init_ex; init.cpp)
+int robust_rotation_average(int d, int n, const double* R, const double* kappa, double threshold, int max_iters,
+                            double mu_step, double* R_opt, double* weights, int* iters, std::string& err);
+int distributed_initialization_ex(int d, int n, int m, const int* p1, const int* p2, const double* R, const double* t,
+                                  const double* kappa, const double* tau, const int* agent_of, int num_agents,
+                                  const dpgo_init_params& P, double* T_local, double* frames, int* parent,
+                                  int* candidates, int* inliers, unsigned char* edge_inlier, int* iters, double* relres,
+                                  std::string& err);
 int distributed_initialization(int d, int n, int m, const int* p1, const int* p2, const double* R, const double* t,
                                const double* kappa, const double* tau, const int* agent_of, int num_agents, bool gpu,
                                double rtol, int max_iters, double* T_out, int* iters, double* relres,

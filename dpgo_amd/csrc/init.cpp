@@ -481,18 +481,17 @@ int chordal_initialization_gpu(int d, int n, int m, const int* p1, const int* p2
   return rc;
 }
 
-int distributed_initialization(int d, int n, int m, const int* p1, const int* p2, const double* R, const double* t,
-                               const double* kappa, const double* tau, const int* agent_of, int num_agents, bool gpu,
-                               double rtol, int max_iters, double* T_out, int* iters, double* relres,
-                               std::string& err) {
-  const int d2 = d * d, b = d + 1;
-  // ---- PGOAgent::localInitialization: chordal on every agent's private graph (all agents in one
-  // block-diagonal system; one anchor per agent, at the agent's BFS centre)
+namespace {
+// PGOAgent::localInitialization for the L2 cost: chordal on every agent's private graph (all agents in one
+// block-diagonal system; one anchor per agent, at the agent's BFS centre).  verts[a]: the poses of agent a, ascending.
+int local_chordal(int d, int n, int m, const int* p1, const int* p2, const double* R, const double* t,
+                  const double* kappa, const double* tau, const int* agent_of, int num_agents,
+                  const std::vector<std::vector<int>>& verts, bool gpu, double rtol, int max_iters, double* Tl,
+                  int* iters, double* relres, std::string& err) {
+  const int d2 = d * d;
   std::vector<int> q1, q2;
   std::vector<double> qR, qt, qk, qtau;
   std::vector<std::vector<int>> adj(n);
-  std::vector<std::vector<int>> verts(num_agents);
-  for (int p = 0; p < n; ++p) verts[agent_of[p]].push_back(p);
   for (int e = 0; e < m; ++e) {
     const int i = p1[e], j = p2[e];
     if (agent_of[i] != agent_of[j]) continue;
@@ -508,15 +507,9 @@ int distributed_initialization(int d, int n, int m, const int* p1, const int* p2
   std::vector<char> anchor(n, 0);
   {
     std::vector<int> dist(n, -1), par(n, -1);
-    for (int a = 0; a < num_agents; ++a) {
-      if (verts[a].empty()) {
-        err = "agent without poses";
-        return -1;
-      }
+    for (int a = 0; a < num_agents; ++a)
       anchor[bfs_centre(adj, verts[a], std::vector<int>(agent_of, agent_of + n), a, dist, par)] = 1;
-    }
   }
-  std::vector<double> Tl(static_cast<size_t>(n) * d * b);
   int it_sum = 0;
   double rr = 0.0;
   auto direct = [](const BlockSys& S, int nr, std::vector<double>& rx, std::string& e) {
@@ -531,19 +524,153 @@ int distributed_initialization(int d, int n, int m, const int* p1, const int* p2
   };
   const int mq = static_cast<int>(q1.size());
   const int rc = gpu ? chordal_core(d, n, mq, q1.data(), q2.data(), qR.data(), qt.data(), qk.data(), qtau.data(),
-                                    anchor, Tl.data(), pcg, err)
+                                    anchor, Tl, pcg, err)
                      : chordal_core(d, n, mq, q1.data(), q2.data(), qR.data(), qt.data(), qk.data(), qtau.data(),
-                                    anchor, Tl.data(), direct, err);
+                                    anchor, Tl, direct, err);
   if (iters) *iters = it_sum;
   if (relres) *relres = rr;
-  if (rc != 0) return rc;
+  return rc;
+}
+}  // namespace
+
+// robustSingleRotationAveraging (src/DPGO_utils.cpp:582-644): GNC-TLS over the chordal mean.  R row-major d*d per
+// item; kappa null = all ones.  R_opt is the estimate solved with the weights of the iteration before the final
+// reweighting (the reference returns that one: converged outliers leave a small trace in it); weights are the final
+// ones (all 1 when GNC is skipped), iters the GNC iterations run.
+int robust_rotation_average(int d, int n, const double* R, const double* kappa, double threshold, int max_iters,
+                            double mu_step, double* R_opt, double* weights, int* iters, std::string& err) {
+  const int d2 = d * d;
+  if (n <= 0) {
+    err = "robust rotation averaging: no rotations";
+    return -1;
+  }
+  for (int i = 0; i < n; ++i) {  // checkRotationMatrix (src/DPGO_utils.cpp:494-500; asserts there)
+    const double* A = R + static_cast<size_t>(i) * d2;
+    const double det = d == 2 ? A[0] * A[3] - A[1] * A[2]
+                              : A[0] * (A[4] * A[8] - A[5] * A[7]) - A[1] * (A[3] * A[8] - A[5] * A[6]) +
+                                    A[2] * (A[3] * A[7] - A[4] * A[6]);
+    double off = 0.0;
+    for (int u = 0; u < d; ++u)
+      for (int v = 0; v < d; ++v) {
+        double s = u == v ? -1.0 : 0.0;
+        for (int w = 0; w < d; ++w) s += A[w * d + u] * A[w * d + v];
+        off += s * s;
+      }
+    if (!(std::fabs(det - 1.0) < 1e-8) || !(std::sqrt(off) < 1e-8)) {
+      err = "robust rotation averaging: item " + std::to_string(i) + " is not a rotation";
+      return -1;
+    }
+  }
+  auto kap = [&](int i) { return kappa ? kappa[i] : 1.0; };
+  auto solve = [&](const double* w) {  // singleRotationAveraging with kappa .* w
+    double M[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (int i = 0; i < n; ++i) {
+      const double k = w ? kap(i) * w[i] : kap(i);
+      for (int x = 0; x < d2; ++x) M[x] += k * R[static_cast<size_t>(i) * d2 + x];
+    }
+    project_rotation(d, M, R_opt);
+  };
+  auto rsq = [&](int i) {
+    double s = 0.0;
+    for (int x = 0; x < d2; ++x) {
+      const double v = R_opt[x] - R[static_cast<size_t>(i) * d2 + x];
+      s += v * v;
+    }
+    return kap(i) * s;
+  };
+  for (int i = 0; i < n; ++i) weights[i] = 1.0;
+  if (iters) *iters = 0;
+  solve(nullptr);
+  double maxr = 0.0;
+  for (int i = 0; i < n; ++i) maxr = std::max(maxr, rsq(i));
+  const double barc_sq = threshold * threshold;
+  double mu = std::min(barc_sq / (2 * maxr - barc_sq), 1e-5);
+  if (!(mu > 0)) return 0;  // small residuals: GNC is skipped
+  const double w_tol = 1e-8;
+  for (int it = 0; it < max_iters; ++it) {
+    solve(weights);
+    int nc = 0;
+    for (int i = 0; i < n; ++i) {
+      // RobustCost::weight for GNC_TLS (src/DPGO_robust.cpp:49-61) of r = sqrt(rSq)
+      const double r = std::sqrt(rsq(i)), r2 = r * r;
+      const double upper = (mu + 1) / mu * barc_sq, lower = mu / (mu + 1) * barc_sq;
+      const double wi = r2 >= upper ? 0.0 : r2 <= lower ? 1.0 : std::sqrt(barc_sq * mu * (mu + 1) / r2) - mu;
+      if (wi < w_tol || wi > 1 - w_tol) ++nc;
+      weights[i] = wi;
+    }
+    if (iters) *iters = it + 1;
+    if (nc == n) break;
+    mu = mu_step * mu;
+  }
+  return 0;
+}
+
+int distributed_initialization_ex(int d, int n, int m, const int* p1, const int* p2, const double* R, const double* t,
+                                  const double* kappa, const double* tau, const int* agent_of, int num_agents,
+                                  const dpgo_init_params& P, double* T_local, double* frames, int* parent,
+                                  int* candidates, int* inliers, unsigned char* edge_inlier, int* iters, double* relres,
+                                  std::string& err) {
+  const int d2 = d * d, b = d + 1;
+  const bool gpu = P.use_gpu != 0;
+  const double rtol = P.rtol;
+  const int max_iters = P.max_iters;
+  if (iters) *iters = 0;
+  if (relres) *relres = 0.0;
+  std::vector<std::vector<int>> verts(num_agents);
+  for (int p = 0; p < n; ++p) verts[agent_of[p]].push_back(p);
+  for (int a = 0; a < num_agents; ++a)
+    if (verts[a].empty()) {
+      err = "agent without poses";
+      return -1;
+    }
+  std::vector<double> Tl(static_cast<size_t>(n) * d * b);
+  if (P.local_init == DPGO_LOCAL_ODOMETRY) {
+    // PGOAgent::localInitialization under a robust cost (src/PGOAgent.cpp:947-962): odometryInitialization, the
+    // agent's odometry edges (consecutive local indices, dpgo_rbcd_weight_owner's rule) composed from its first pose
+    std::vector<int> local(n), odo(n, -1);  // odo[p]: the edge from pose p to the agent's next pose
+    for (int a = 0; a < num_agents; ++a)
+      for (size_t l = 0; l < verts[a].size(); ++l) local[verts[a][l]] = static_cast<int>(l);
+    for (int e = 0; e < m; ++e)
+      if (agent_of[p1[e]] == agent_of[p2[e]] && local[p2[e]] == local[p1[e]] + 1 && odo[p1[e]] < 0) odo[p1[e]] = e;
+    for (int a = 0; a < num_agents; ++a) {
+      double* T0 = &Tl[static_cast<size_t>(verts[a][0]) * d * b];
+      for (int x = 0; x < d * b; ++x) T0[x] = 0.0;
+      for (int u = 0; u < d; ++u) T0[u * d + u] = 1.0;
+      for (size_t l = 0; l + 1 < verts[a].size(); ++l) {
+        const int e = odo[verts[a][l]];
+        if (e < 0) {
+          err = "odometry initialisation: the odometry of agent " + std::to_string(a) + " stops at its pose " +
+                std::to_string(l) + ": no edge joins it to the next (contiguous pose ranges are the supported partitions)";
+          return -1;
+        }
+        const double* Ts = &Tl[static_cast<size_t>(verts[a][l]) * d * b];  // column-major d x b
+        double* Td = &Tl[static_cast<size_t>(verts[a][l + 1]) * d * b];
+        const double* Re = R + static_cast<size_t>(e) * d2;
+        const double* te = t + static_cast<size_t>(e) * d;
+        for (int u = 0; u < d; ++u) {
+          for (int c = 0; c < d; ++c) {
+            double s = 0.0;
+            for (int w = 0; w < d; ++w) s += Ts[w * d + u] * Re[w * d + c];
+            Td[c * d + u] = s;
+          }
+          double s = 0.0;
+          for (int w = 0; w < d; ++w) s += Ts[w * d + u] * te[w];
+          Td[d * d + u] = Ts[d * d + u] + s;
+        }
+      }
+    }
+  } else {
+    const int rc = local_chordal(d, n, m, p1, p2, R, t, kappa, tau, agent_of, num_agents, verts, gpu, rtol, max_iters,
+                                 Tl.data(), iters, relres, err);
+    if (rc != 0) return rc;
+  }
   auto Rl = [&](int p, int u, int c) { return Tl[(static_cast<size_t>(p) * b + c) * d + u]; };  // R_loc(u, c)
   auto tl = [&](int p, int u) { return Tl[(static_cast<size_t>(p) * b + d) * d + u]; };
   // ---- initializeInGlobalFrame: agents join the frame of the agent holding pose 0 in breadth-first
-  // order over the agent graph; each takes the L2 average, over its shared loop closures with agents
+  // order over the agent graph.  DPGO_ALIGN_L2: each takes the L2 average, over its shared loop closures with agents
   // already in the frame, of the frame transform every closure implies (rotations: chordal mean
-  // projected to SO(d); translations: tau-weighted mean).  The reference averages robustly (GNC-TLS,
-  // robustSinglePoseAveraging); on outlier-free data the two coincide.
+  // projected to SO(d); translations: tau-weighted mean).  DPGO_ALIGN_ROBUST_TWO_STAGE: the reference's
+  // computeRobustNeighborTransformTwoStage (src/PGOAgent.cpp:290-331) against the one agent being dequeued.
   std::vector<std::vector<int>> shared(num_agents);
   std::vector<std::set<int>> nbr(num_agents);
   for (int e = 0; e < m; ++e) {
@@ -559,6 +686,12 @@ int distributed_initialization(int d, int n, int m, const int* p1, const int* p2
   std::vector<int> order{agent_of[0]};
   done[agent_of[0]] = 1;
   for (int u = 0; u < d; ++u) FR[static_cast<size_t>(agent_of[0]) * d2 + u * d + u] = 1.0;
+  for (int a = 0; a < num_agents; ++a) {
+    parent[a] = -1;
+    candidates[a] = 0;
+    inliers[a] = 0;
+  }
+  if (edge_inlier) std::fill(edge_inlier, edge_inlier + m, static_cast<unsigned char>(255));
   // world pose of a pose of an aligned agent
   auto world = [&](int p, double* Rw, double* tw) {
     const int a = agent_of[p];
@@ -574,12 +707,14 @@ int distributed_initialization(int d, int n, int m, const int* p1, const int* p2
       tw[u] = s;
     }
   };
+  const bool robust = P.align == DPGO_ALIGN_ROBUST_TWO_STAGE;
   for (size_t h = 0; h < order.size(); ++h) {
     for (int A : nbr[order[h]]) {
       if (done[A]) continue;
-      // closures of A to agents already in the frame: implied world pose of A's endpoint
+      // closures of A to agents already in the frame (robust: to the dequeued agent only, the reference's one
+      // neighborID): implied world pose of A's endpoint
       struct Est {
-        int p;
+        int p, e;
         double Rw[9], tw[3], w, wk;
       };
       std::vector<Est> est;
@@ -587,13 +722,14 @@ int distributed_initialization(int d, int n, int m, const int* p1, const int* p2
         const int i = p1[e], j = p2[e];
         const bool a_is_j = agent_of[j] == A;
         const int other = a_is_j ? i : j;
-        if (!done[agent_of[other]]) continue;
+        if (robust ? agent_of[other] != order[h] : !done[agent_of[other]]) continue;
         double Ro[9], to[3];
         world(other, Ro, to);
         const double* Re = R + static_cast<size_t>(e) * d2;
         const double* te = t + static_cast<size_t>(e) * d;
         Est x;
         x.p = a_is_j ? j : i;
+        x.e = e;
         x.w = tau[e];
         x.wk = kappa[e];
         for (int u = 0; u < d; ++u)
@@ -610,48 +746,128 @@ int distributed_initialization(int d, int n, int m, const int* p1, const int* p2
         est.push_back(x);
       }
       if (est.empty()) continue;
-      // rotation: chordal mean of Rw R_loc^T (kappa-weighted) projected to SO(d)
-      double M[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-      for (const auto& x : est) {
-        const double k = x.wk;
-        for (int u = 0; u < d; ++u)
-          for (int c = 0; c < d; ++c) {
-            double s = 0.0;
-            for (int w = 0; w < d; ++w) s += x.Rw[u * d + w] * Rl(x.p, c, w);
-            M[u * d + c] += k * s;
-          }
-      }
       double* F = &FR[static_cast<size_t>(A) * d2];
-      project_rotation(d, M, F);
-      double tsum[3] = {0, 0, 0}, wsum = 0.0;
-      for (const auto& x : est) {
-        for (int u = 0; u < d; ++u) {
-          double s = 0.0;
-          for (int w = 0; w < d; ++w) s += F[u * d + w] * tl(x.p, w);
-          tsum[u] += x.w * (x.tw[u] - s);
+      if (robust) {
+        // computeNeighborTransform (:250-288) per closure: F_i = W_A-pose T_local(A-pose)^-1; rotations averaged by
+        // GNC-TLS with unit kappa, translation = the plain mean over the inlier candidates
+        const int nc = static_cast<int>(est.size());
+        std::vector<double> cR(static_cast<size_t>(nc) * d2), ct(static_cast<size_t>(nc) * d), wts(nc);
+        for (int x = 0; x < nc; ++x) {
+          double* Fi = &cR[static_cast<size_t>(x) * d2];
+          for (int u = 0; u < d; ++u)
+            for (int c = 0; c < d; ++c) {
+              double s = 0.0;
+              for (int w = 0; w < d; ++w) s += est[x].Rw[u * d + w] * Rl(est[x].p, c, w);
+              Fi[u * d + c] = s;
+            }
+          for (int u = 0; u < d; ++u) {
+            double s = 0.0;
+            for (int w = 0; w < d; ++w) s += Fi[u * d + w] * tl(est[x].p, w);
+            ct[static_cast<size_t>(x) * d + u] = est[x].tw[u] - s;
+          }
         }
-        wsum += x.w;
+        double Fopt[9];
+        if (robust_rotation_average(d, nc, cR.data(), nullptr, P.max_rotation_error, P.gnc_max_iters, P.gnc_mu_step,
+                                    Fopt, wts.data(), nullptr, err) != 0)
+          return -1;
+        int ni = 0;
+        double tsum[3] = {0, 0, 0};
+        for (int x = 0; x < nc; ++x) {
+          const bool in = wts[x] > 1 - 1e-8;
+          if (edge_inlier) edge_inlier[est[x].e] = in ? 1 : 0;
+          if (!in) continue;
+          ++ni;
+          for (int u = 0; u < d; ++u) tsum[u] += ct[static_cast<size_t>(x) * d + u];
+        }
+        if (ni == 0) continue;  // "abort and wait to try again": A waits for another aligned neighbour
+        std::memcpy(F, Fopt, sizeof(double) * d2);
+        for (int u = 0; u < d; ++u) Ft[static_cast<size_t>(A) * d + u] = tsum[u] / ni;
+        inliers[A] = ni;
+      } else {
+        // rotation: chordal mean of Rw R_loc^T (kappa-weighted) projected to SO(d)
+        double M[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+        for (const auto& x : est) {
+          const double k = x.wk;
+          for (int u = 0; u < d; ++u)
+            for (int c = 0; c < d; ++c) {
+              double s = 0.0;
+              for (int w = 0; w < d; ++w) s += x.Rw[u * d + w] * Rl(x.p, c, w);
+              M[u * d + c] += k * s;
+            }
+        }
+        project_rotation(d, M, F);
+        double tsum[3] = {0, 0, 0}, wsum = 0.0;
+        for (const auto& x : est) {
+          for (int u = 0; u < d; ++u) {
+            double s = 0.0;
+            for (int w = 0; w < d; ++w) s += F[u * d + w] * tl(x.p, w);
+            tsum[u] += x.w * (x.tw[u] - s);
+          }
+          wsum += x.w;
+          if (edge_inlier) edge_inlier[x.e] = 1;
+        }
+        for (int u = 0; u < d; ++u) Ft[static_cast<size_t>(A) * d + u] = tsum[u] / wsum;
+        inliers[A] = static_cast<int>(est.size());
       }
-      for (int u = 0; u < d; ++u) Ft[static_cast<size_t>(A) * d + u] = tsum[u] / wsum;
+      parent[A] = order[h];
+      candidates[A] = static_cast<int>(est.size());
       done[A] = 1;
       order.push_back(A);
     }
   }
   for (int a = 0; a < num_agents; ++a)
     if (!done[a]) {
-      err = "agent graph is not connected (an agent shares no loop closure with the others)";
+      err = robust ? "agent " + std::to_string(a) +
+                         " was never aligned (no shared loop closure with an aligned agent, or no inlier among them)"
+                   : "agent graph is not connected (an agent shares no loop closure with the others)";
       return -1;
     }
-  for (int p = 0; p < n; ++p) {
-    double Rw[9], tw[3];
-    world(p, Rw, tw);
+  std::memcpy(T_local, Tl.data(), sizeof(double) * Tl.size());
+  for (int a = 0; a < num_agents; ++a) {  // d x (d+1) column-major per agent
+    double* F = frames + static_cast<size_t>(a) * d * b;
     for (int u = 0; u < d; ++u) {
-      for (int c = 0; c < d; ++c) T_out[(static_cast<size_t>(p) * b + c) * d + u] = Rw[u * d + c];
-      T_out[(static_cast<size_t>(p) * b + d) * d + u] = tw[u];
+      for (int c = 0; c < d; ++c) F[c * d + u] = FR[static_cast<size_t>(a) * d2 + u * d + c];
+      F[d * d + u] = Ft[static_cast<size_t>(a) * d + u];
     }
   }
   return 0;
 }
+
+// The multi-robot initialisation with its defaults (per-agent chordal, L2 alignment) as one global trajectory:
+// T_out = frame o local per pose, the operations of world() above in the same order.
+int distributed_initialization(int d, int n, int m, const int* p1, const int* p2, const double* R, const double* t,
+                               const double* kappa, const double* tau, const int* agent_of, int num_agents, bool gpu,
+                               double rtol, int max_iters, double* T_out, int* iters, double* relres,
+                               std::string& err) {
+  const int b = d + 1;
+  dpgo_init_params P;
+  dpgo_default_init_params(&P);
+  P.use_gpu = gpu ? 1 : 0;
+  P.rtol = rtol;
+  P.max_iters = max_iters;
+  std::vector<double> Tl(static_cast<size_t>(n) * d * b), fr(static_cast<size_t>(num_agents) * d * b);
+  std::vector<int> par(num_agents), cand(num_agents), inl(num_agents);
+  const int rc = distributed_initialization_ex(d, n, m, p1, p2, R, t, kappa, tau, agent_of, num_agents, P, Tl.data(),
+                                               fr.data(), par.data(), cand.data(), inl.data(), nullptr, iters, relres,
+                                               err);
+  if (rc != 0) return rc;
+  for (int p = 0; p < n; ++p) {
+    const double* F = &fr[static_cast<size_t>(agent_of[p]) * d * b];
+    const double* L = &Tl[static_cast<size_t>(p) * d * b];
+    for (int u = 0; u < d; ++u) {
+      for (int c = 0; c < d; ++c) {
+        double s = 0.0;
+        for (int w = 0; w < d; ++w) s += F[w * d + u] * L[c * d + w];
+        T_out[(static_cast<size_t>(p) * b + c) * d + u] = s;
+      }
+      double s = F[d * d + u];
+      for (int w = 0; w < d; ++w) s += F[w * d + u] * L[d * d + w];
+      T_out[(static_cast<size_t>(p) * b + d) * d + u] = s;
+    }
+  }
+  return 0;
+}
+
 
 void project_to_rotation(int d, const double* M, double* out) { project_rotation(d, M, out); }
 

@@ -450,6 +450,15 @@ hipError_t launch_polar_comb(int r, int b, const LaunchCtx& c, const double* A, 
 // No tile set: any n >= 1; T must not overlap X.
 hipError_t launch_round_se(int r, int b, long n, const double* X, const double* anchor, double* T,
                            hipStream_t stream);
+// The inverse of launch_round_se: out (r x b per pose) = YLift [F_R R_j | F_R t_j + F_t] of the n SE(d) poses T (d x b
+// per pose, column-major), F = frames[frame_of[j]] (d x b column-major per entry); frames and frame_of both null:
+// out = YLift T.  YLift (r x d column-major) travels in the kernel arguments.  No tile set: any n >= 1; out must not
+// overlap the inputs; frame_of's entries must index frames.
+struct FrameLiftY {
+  double v[24];  // r x d column-major, r <= 8, d <= 3
+};
+hipError_t launch_frame_lift(int r, int b, long n, const double* T, const FrameLiftY& ylift, const double* frames,
+                             const int* frame_of, double* out, hipStream_t stream);
 // Rank staircase: out ((r + 1) x b per pose) = Retr_[X; 0](alpha [0; v^T]) of the n lifted poses X (r x b per pose),
 // v the (b n)-vector of the direction (pose j's slice v[b j .. b j + b)): out_j = [qf([Y_j; alpha v_Y^T]) |
 // (p_j; alpha v_p)] with k_retract's qf.  v null: the plain lift [X; 0], bitwise.  No tile set: any n >= 1; rank

@@ -2816,6 +2816,101 @@ __global__ __launch_bounds__(64) void k_lift_escape(long n, const double* __rest
   }
 }
 
+// The inverse of k_round_se: lift SE(d) poses to rank R, each composed with a frame first (the engine's read-in of a
+// per-agent initialisation or a warm start; PGOAgent::initializeInGlobalFrame's T_world2_world1 T then X = YLift T,
+// src/PGOAgent.cpp:402-415).  Per pose j with T_j = [R_j | t_j] (D x B column-major) and F = frames[frame_of[j]]
+// ([F_R | F_t], D x B column-major):
+//   W = [F_R R_j | F_R t_j + F_t],   out_j = YLift W   (R x B column-major);
+// frames == nullptr (block-uniform): W = T_j, T's entries only pass through the YLift product.  k_round_se's shape:
+// block k takes poses [64 k, 64 k + 64); the D B-wide span streams through LDS coalesced (16-byte chunks where the
+// span width is even, the block full and the span aligned, 8-byte otherwise), thread t works on pose t, and the R B-wide
+// result streams out of the same LDS.  Row strides are the span widths made odd (conflict-free b64 reads).  The frame
+// table is a few entries read at (mostly wave-uniform) addresses: agent-contiguous spans hit one entry.
+template <int R, int B>
+__global__ __launch_bounds__(64) void k_frame_lift(long n, const double* __restrict__ T, FrameLiftY yl,
+                                                   const double* __restrict__ frames,
+                                                   const int* __restrict__ frame_of, double* __restrict__ out) {
+  constexpr int D = B - 1;
+  constexpr int PW = D * B, PS = PW | 1;  // D (D + 1) is even
+  constexpr int OW = R * B, OS = OW | 1;
+  static_assert(PS <= OS, "the lifted poses reuse the staged span's LDS");
+  __shared__ double sm[64 * OS];
+  const int t = static_cast<int>(threadIdx.x);
+  const long first = static_cast<long>(blockIdx.x) * 64;
+  if (first >= n) return;
+  const int count = n - first < 64 ? static_cast<int>(n - first) : 64;
+  const double* src = T + first * PW;
+  double* dst = out + first * OW;
+  const bool full = count == 64;
+  if (full && (reinterpret_cast<unsigned long>(src) & 15) == 0) {
+    constexpr int NV = PW / 2;  // 16-byte chunks per lane (PW even: a chunk never straddles two poses)
+    const double2* S2 = reinterpret_cast<const double2*>(src);
+    double2 w[NV];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) w[i] = S2[t + 64 * i];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int x = 2 * (t + 64 * i);
+      double* q = sm + (x / PW) * PS + x % PW;
+      q[0] = w[i].x;
+      q[1] = w[i].y;
+    }
+  } else {
+    const int total = count * PW;
+    for (int x = t; x < total; x += 64) sm[(x / PW) * PS + x % PW] = src[x];
+  }
+  __syncthreads();
+  const bool own = t < count;
+  double W[D][B];
+  if (own) {
+    const double* ps = sm + t * PS;
+    if (frames != nullptr) {  // block-uniform
+      const double* F = frames + static_cast<long>(frame_of[first + t]) * PW;
+#pragma unroll
+      for (int c = 0; c < B; ++c)
+#pragma unroll
+        for (int u = 0; u < D; ++u) {
+          double s = c == D ? F[D * D + u] : 0.0;
+#pragma unroll
+          for (int k = 0; k < D; ++k) s = fma(F[k * D + u], ps[c * D + k], s);
+          W[u][c] = s;
+        }
+    } else {
+#pragma unroll
+      for (int c = 0; c < B; ++c)
+#pragma unroll
+        for (int u = 0; u < D; ++u) W[u][c] = ps[c * D + u];
+    }
+  }
+  __syncthreads();  // every pose of the span is in registers: its LDS now takes the lifted poses
+  if (own) {
+    double* po = sm + t * OS;
+#pragma unroll
+    for (int c = 0; c < B; ++c)
+#pragma unroll
+      for (int a = 0; a < R; ++a) {
+        double s = 0.0;
+#pragma unroll
+        for (int u = 0; u < D; ++u) s = fma(yl.v[u * R + a], W[u][c], s);
+        po[c * R + a] = s;
+      }
+  }
+  __syncthreads();
+  if (OW % 2 == 0 && full && (reinterpret_cast<unsigned long>(dst) & 15) == 0) {
+    constexpr int NO = OW / 2;
+    double2* O2 = reinterpret_cast<double2*>(dst);
+#pragma unroll
+    for (int i = 0; i < NO; ++i) {
+      const int x = 2 * (t + 64 * i);
+      const double* q = sm + (x / OW) * OS + x % OW;
+      O2[t + 64 * i] = make_double2(q[0], q[1]);
+    }
+  } else {
+    const int total_out = count * OW;
+    for (int x = t; x < total_out; x += 64) dst[x] = sm[(x / OW) * OS + x % OW];
+  }
+}
+
 // Nesterov updateV deferred into the colour's next combination pass (one pass instead of two):
 //   V' = project(V + gv (X - Yv))   (updateV, src/PGOAgent.cpp:1086-1091, of the agent's last update)
 //   out = project(sa X + sb V')     (updateY / the iterate(false) step, :1077-1084, of the next iteration)
@@ -5150,6 +5245,17 @@ hipError_t launch_lift_escape(int r, int b, long n, const double* X, const doubl
   if (blocks > 0x7fffffffL) return hipErrorInvalidValue;
   const dim3 grid(static_cast<unsigned>(blocks));
   DPGO_DISPATCH(r, b, (k_lift_escape<R, B><<<grid, 64, 0, stream>>>(n, X, v, alpha, out)));
+  return hipGetLastError();
+}
+
+hipError_t launch_frame_lift(int r, int b, long n, const double* T, const FrameLiftY& ylift, const double* frames,
+                             const int* frame_of, double* out, hipStream_t stream) {
+  if (n <= 0 || T == nullptr || out == nullptr || (frames == nullptr) != (frame_of == nullptr))
+    return hipErrorInvalidValue;
+  const long blocks = (n + 63) / 64;
+  if (blocks > 0x7fffffffL) return hipErrorInvalidValue;
+  const dim3 grid(static_cast<unsigned>(blocks));
+  DPGO_DISPATCH(r, b, (k_frame_lift<R, B><<<grid, 64, 0, stream>>>(n, T, ylift, frames, frame_of, out)));
   return hipGetLastError();
 }
 

@@ -125,6 +125,11 @@ struct dpgo_rbcd_s {
   int n_global = 0;
   std::vector<int> own_of_global;  // global pose id -> owned buffer pose index, -1 = another rank's
   DevBuf<double> Tround;           // the owned poses rounded to SE(d), d x b per pose
+  // trajectory read-in (dpgo_rbcd_set_trajectory): the owned poses' d x b blocks, then the K frames, staged for
+  // k_frame_lift; the owned poses' global agent ids, built at the first call with frames
+  DevBuf<double> Tin;
+  DevBuf<int> agent_of_own;
+  bool agent_of_own_valid = false;
   // per colour: the problem edges whose weight this rank reports (dpgo_rbcd_weight_owner's rule: private loop
   // closures and the shared ones whose other agent has the larger ID) with their index in the graph's edge order
   struct WMap {
@@ -839,17 +844,11 @@ static int join_side(dpgo_rbcd e) {
   return DPGO_HIP_OK;
 }
 
-int dpgo_rbcd_set_X(dpgo_rbcd e, const double* Xg) {
-  if (!e || !Xg) return fail(DPGO_HIP_EINVAL, "null argument");
-  DPGO_TRY(join_side(e));
-  const size_t rbs = e->rb();
-  std::vector<double> host(std::max<size_t>(static_cast<size_t>(e->Nown) * rbs, 1));
-  for (long q = 0; q < e->Nown; ++q)
-    std::memcpy(&host[q * rbs], Xg + static_cast<size_t>(e->own_global[q]) * rbs, sizeof(double) * rbs);
-  const size_t bytes = sizeof(double) * e->Nown * rbs;
+// PGOAgent::setX -> initializeAcceleration (:55-68, :1062-1071) once X is queued on the engine stream:
+// XPrev = V = Y = X, and the iteration state of a fresh engine
+static int reset_from_X(dpgo_rbcd e) {
+  const size_t bytes = sizeof(double) * e->Nown * e->rb();
   if (bytes) {
-    HIP_TRY(hipMemcpyAsync(e->X.p, host.data(), bytes, hipMemcpyHostToDevice, e->stream));
-    // PGOAgent::setX -> initializeAcceleration (:55-68, :1062-1071): XPrev = V = Y = X
     HIP_TRY(hipMemcpyAsync(e->Y.p, e->X.p, bytes, hipMemcpyDeviceToDevice, e->stream));
     HIP_TRY(hipMemcpyAsync(e->V.p, e->X.p, bytes, hipMemcpyDeviceToDevice, e->stream));
     HIP_TRY(hipMemcpyAsync(e->Xprev.p, e->X.p, bytes, hipMemcpyDeviceToDevice, e->stream));
@@ -862,6 +861,49 @@ int dpgo_rbcd_set_X(dpgo_rbcd e, const double* Xg) {
   e->next_y.valid = false;
   std::fill(e->v_pending.begin(), e->v_pending.end(), 0);
   return DPGO_HIP_OK;
+}
+
+int dpgo_rbcd_set_X(dpgo_rbcd e, const double* Xg) {
+  if (!e || !Xg) return fail(DPGO_HIP_EINVAL, "null argument");
+  DPGO_TRY(join_side(e));
+  const size_t rbs = e->rb();
+  std::vector<double> host(std::max<size_t>(static_cast<size_t>(e->Nown) * rbs, 1));
+  for (long q = 0; q < e->Nown; ++q)
+    std::memcpy(&host[q * rbs], Xg + static_cast<size_t>(e->own_global[q]) * rbs, sizeof(double) * rbs);
+  const size_t bytes = sizeof(double) * e->Nown * rbs;
+  if (bytes) HIP_TRY(hipMemcpyAsync(e->X.p, host.data(), bytes, hipMemcpyHostToDevice, e->stream));
+  return reset_from_X(e);
+}
+
+int dpgo_rbcd_set_trajectory(dpgo_rbcd e, const double* Tg, const double* YLift, const double* frames) {
+  if (!e || !Tg || !YLift) return fail(DPGO_HIP_EINVAL, "null argument");
+  DPGO_TRY(join_side(e));
+  std::vector<double> host;  // both live until reset_from_X has synchronised
+  std::vector<int> ag;
+  if (e->Nown) {
+    const size_t dbs = static_cast<size_t>(e->d) * e->b, nd = static_cast<size_t>(e->Nown) * dbs;
+    // only the owned poses' d x b blocks cross the bus; the frames are staged behind them
+    host.resize(nd);
+    for (long q = 0; q < e->Nown; ++q)
+      std::memcpy(&host[q * dbs], Tg + static_cast<size_t>(e->own_global[q]) * dbs, sizeof(double) * dbs);
+    HIP_TRY(e->Tin.ensure(nd + static_cast<size_t>(e->K) * dbs));
+    HIP_TRY(hipMemcpyAsync(e->Tin.p, host.data(), sizeof(double) * nd, hipMemcpyHostToDevice, e->stream));
+    const double* frames_dev = nullptr;
+    if (frames) {
+      HIP_TRY(hipMemcpyAsync(e->Tin.p + nd, frames, sizeof(double) * e->K * dbs, hipMemcpyHostToDevice, e->stream));
+      frames_dev = e->Tin.p + nd;
+      if (!e->agent_of_own_valid) {  // once per engine: the owned poses' global agent ids
+        ag.resize(e->Nown);
+        for (size_t k = 0; k < e->owned.size(); ++k)
+          std::fill(ag.begin() + e->own_pose_off[k], ag.begin() + e->own_pose_off[k + 1], e->owned[k]);
+        DPGO_TRY(upload_vec(e->agent_of_own, ag, e->stream));
+        e->agent_of_own_valid = true;
+      }
+    }
+    DPGO_TRY(dpgo_hip_frame_lift_dev(e->r, e->d, e->Nown, e->Tin.p, YLift, frames_dev, e->K,
+                                     frames ? e->agent_of_own.p : nullptr, e->X.p, e->stream));
+  }
+  return reset_from_X(e);
 }
 
 int dpgo_rbcd_get_X(dpgo_rbcd e, double* Xg) {

@@ -93,6 +93,9 @@ _SIGS = [
     ("dpgo_hip_round_se", [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp], C.c_int),
     ("dpgo_hip_round_se_dev", [C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
      C.c_int),
+    ("dpgo_hip_frame_lift", [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _ip, _dp], C.c_int),
+    ("dpgo_hip_frame_lift_dev", [C.c_int, C.c_int, C.c_longlong, C.c_void_p, _dp, C.c_void_p, C.c_int, C.c_void_p,
+                                 C.c_void_p, C.c_void_p], C.c_int),
     ("dpgo_hip_lift_escape", [C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_double, _dp], C.c_int),
     ("dpgo_hip_lift_escape_dev", [C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p,
                                   C.c_void_p], C.c_int),
@@ -550,6 +553,47 @@ def round_se_dev(r, d, n, X_dev: int, anchor_dev: int | None, T_dev: int, stream
                                        C.c_void_p(T_dev), C.c_void_p(stream_ptr or 0)))
 
 
+def _ylift_colmajor(YLift, r, d):
+    Y = np.asarray(YLift, dtype=np.float64)
+    if Y.shape != (r, d):
+        raise DPGOHipError(f"YLift must be r x d = {r} x {d}")
+    return _f64(Y.T.ravel())
+
+
+def frame_lift(T, YLift, frames=None, frame_of=None):
+    """The inverse of round_se: X (r x (d+1) n) = YLift [F_R R_j | F_R t_j + F_t] per pose of the SE(d) trajectory T
+    (d x (d+1) n), F = frames[frame_of[j]] (frames: nf x d x (d+1), each [F_R | F_t]; frame_of: one int per pose).
+    frames and frame_of both None: X = YLift T."""
+    T = np.asarray(T, dtype=np.float64)
+    d = T.shape[0]
+    n = T.shape[1] // (d + 1)
+    r = np.asarray(YLift).shape[0]
+    t, tp = _f64(to_dev_layout(T))
+    Y, Yp = _ylift_colmajor(YLift, r, d)
+    fp, fop, nf = None, None, 0
+    if frames is not None:
+        F = np.asarray(frames, dtype=np.float64).reshape(-1, d, d + 1)
+        nf = F.shape[0]
+        f, fp = _f64(np.ascontiguousarray(F.transpose(0, 2, 1)).ravel())  # column-major per frame
+    if frame_of is not None:
+        fo, fop = _i32(frame_of)
+        if fo.size != n:
+            raise DPGOHipError("frame_lift: frame_of must have one entry per pose")
+    o = np.empty(n * r * (d + 1))
+    _check(lib().dpgo_hip_frame_lift(r, d, n, tp, Yp, fp, nf, fop, o.ctypes.data_as(_dp)))
+    return from_dev_layout(o, r)
+
+
+def frame_lift_dev(r, d, n, T_dev: int, YLift, frames_dev: int | None, nf, frame_of_dev: int | None, X_out_dev: int,
+                   stream_ptr: int | None = None):
+    """frame_lift on device pointers (YLift: the host r x d matrix), queued on `stream_ptr` (None = the null stream)
+    without synchronisation."""
+    Y, Yp = _ylift_colmajor(YLift, int(r), int(d))
+    _check(lib().dpgo_hip_frame_lift_dev(int(r), int(d), int(n), C.c_void_p(T_dev), Yp, C.c_void_p(frames_dev or 0),
+                                         int(nf), C.c_void_p(frame_of_dev or 0), C.c_void_p(X_out_dev),
+                                         C.c_void_p(stream_ptr or 0)))
+
+
 def escape_params(**kw) -> EscapeParams:
     p = EscapeParams()
     lib().dpgo_hip_default_escape_params(C.byref(p))
@@ -617,6 +661,17 @@ class RbcdParams(C.Structure):
                 ("status", C.c_int), ("rel_change_tol", C.c_double), ("min_convergence_ratio", C.c_double)]
 
 
+class InitParams(C.Structure):
+    """dpgo_init_params (include/dpgo_rbcd.h)."""
+    _fields_ = [("local_init", C.c_int), ("align", C.c_int), ("max_rotation_error", C.c_double),
+                ("gnc_max_iters", C.c_int), ("gnc_mu_step", C.c_double), ("use_gpu", C.c_int), ("rtol", C.c_double),
+                ("max_iters", C.c_int)]
+
+
+LOCAL_INIT = {"chordal": 0, "odometry": 1}
+ALIGN = {"l2": 0, "robust": 1}
+_ubp = C.POINTER(C.c_ubyte)
+
 _lp = C.POINTER(C.c_longlong)
 _SIGS2 = [
     ("dpgo_graph_read_g2o", [C.c_char_p, C.POINTER(C.c_void_p)], C.c_int),
@@ -642,6 +697,11 @@ _SIGS2 = [
     ("dpgo_graph_chordal_init_gpu", [C.c_void_p, C.c_int, _dp, C.c_double, C.c_int, _dp, _ip, _dp], C.c_int),
     ("dpgo_graph_distributed_init", [C.c_void_p, C.c_int, _ip, C.c_int, _dp, C.c_int, C.c_double, C.c_int, _dp, _ip,
                                      _dp], C.c_int),
+    ("dpgo_robust_rotation_average", [C.c_int, C.c_int, _dp, _dp, C.c_double, C.c_int, C.c_double, _dp, _dp, _ip],
+     C.c_int),
+    ("dpgo_default_init_params", [C.POINTER(InitParams)], None),
+    ("dpgo_graph_distributed_init_ex", [C.c_void_p, C.c_int, _ip, C.POINTER(InitParams), _dp, _dp, _ip, _ip, _ip, _ubp,
+                                        _ip, _dp], C.c_int),
     ("dpgo_rbcd_default_params", [C.POINTER(RbcdParams)], None),
     ("dpgo_rbcd_plan", [C.c_void_p, C.c_int, _ip, _ip, C.c_int, C.c_int, _lp, _lp, _ip, _ip], C.c_int),
     ("dpgo_rbcd_create", [C.c_void_p, C.c_int, _ip, _ip, C.c_int, C.c_int, C.POINTER(RbcdParams),
@@ -653,6 +713,7 @@ _SIGS2 = [
     ("dpgo_rbcd_exchange_counts", [C.c_void_p, _lp, _lp], C.c_int),
     ("dpgo_rbcd_set_X", [C.c_void_p, _dp], C.c_int),
     ("dpgo_rbcd_get_X", [C.c_void_p, _dp], C.c_int),
+    ("dpgo_rbcd_set_trajectory", [C.c_void_p, _dp, _dp, _dp], C.c_int),
     ("dpgo_rbcd_get_anchor", [C.c_void_p, C.c_int, _dp, _ip], C.c_int),
     ("dpgo_rbcd_get_trajectory", [C.c_void_p, _dp, _dp], C.c_int),
     ("dpgo_rbcd_get_weights", [C.c_void_p, _dp], C.c_int),
@@ -797,6 +858,39 @@ class Graph:
                                                  int(max_iters), out.ctypes.data_as(_dp), C.byref(it), C.byref(rr)))
         return (out if dev_layout else from_dev_layout(out, r)), it.value, rr.value
 
+    def distributed_init_ex(self, agent_of_pose, local="chordal", align="l2", max_rotation_error=None,
+                            gnc_max_iters=None, gnc_mu_step=None, gpu=False, rtol=1e-12, max_iters=20000):
+        """The multi-robot initialisation as local trajectories plus frames (dpgo_graph_distributed_init_ex):
+        local "chordal" | "odometry" (what the reference does under a robust cost), align "l2" | "robust" (GNC-TLS
+        rotation averaging against the single breadth-first parent, translation mean over the inliers).  Returns
+        (T_local d x (d+1) n, frames K x d x (d+1), info dict(parent, candidates, inliers [K], edge_inlier [m]: 1 inlier
+        candidate / 0 rejected / 255 unused, iters, relres)); Rbcd.set_trajectory and frame_lift take them as they
+        are."""
+        aop, ap = _i32(agent_of_pose)
+        K, d = int(aop.max()) + 1, self.d
+        P = InitParams()
+        lib().dpgo_default_init_params(C.byref(P))
+        P.local_init, P.align = LOCAL_INIT[local], ALIGN[align]
+        if max_rotation_error is not None:
+            P.max_rotation_error = float(max_rotation_error)
+        if gnc_max_iters is not None:
+            P.gnc_max_iters = int(gnc_max_iters)
+        if gnc_mu_step is not None:
+            P.gnc_mu_step = float(gnc_mu_step)
+        P.use_gpu, P.rtol, P.max_iters = int(bool(gpu)), float(rtol), int(max_iters)
+        T = np.empty(self.n * d * (d + 1))
+        F = np.empty(K * d * (d + 1))
+        par = np.empty(K, np.int32); cand = np.empty(K, np.int32); inl = np.empty(K, np.int32)
+        ei = np.empty(max(self.m, 1), np.uint8)
+        it, rr = C.c_int(), C.c_double()
+        _check(lib().dpgo_graph_distributed_init_ex(self.h, K, ap, C.byref(P), T.ctypes.data_as(_dp),
+                                                    F.ctypes.data_as(_dp), par.ctypes.data_as(_ip),
+                                                    cand.ctypes.data_as(_ip), inl.ctypes.data_as(_ip),
+                                                    ei.ctypes.data_as(_ubp), C.byref(it), C.byref(rr)))
+        frames = np.ascontiguousarray(F.reshape(K, d + 1, d).transpose(0, 2, 1))
+        return from_dev_layout(T, d), frames, dict(parent=par, candidates=cand, inliers=inl,
+                                                   edge_inlier=ei[:self.m], iters=it.value, relres=rr.value)
+
     def chain_init_dev_layout(self, r, YLift):
         Y, Yp = _f64(np.asarray(YLift, dtype=np.float64).T.ravel())
         out = np.empty(self.n * (self.d + 1) * r)
@@ -853,6 +947,26 @@ class Graph:
         out = np.empty(self.n, np.int32)
         _check(lib().dpgo_graph_grid_partition(self.h, int(agents_per_axis), out.ctypes.data_as(_ip)))
         return out
+
+
+def robust_rotation_average(R, kappa=None, threshold=None, max_iters=1000, mu_step=1.4):
+    """robustSingleRotationAveraging (src/DPGO_utils.cpp:582-644), host: GNC-TLS over the chordal mean of the
+    rotations R (n x d x d); threshold: chordal, default angular2ChordalSO3(0.5).  Returns (R_opt d x d -- the estimate
+    before the final reweighting, as in the reference -- weights [n], GNC iterations)."""
+    Rs = np.asarray(R, dtype=np.float64)
+    n, d = Rs.shape[0], Rs.shape[-1]
+    rr, rp = _f64(Rs.reshape(-1))
+    kp = None
+    if kappa is not None:
+        kk, kp = _f64(kappa)
+        if kk.size != n:
+            raise DPGOHipError("kappa must have one entry per rotation")
+    if threshold is None:
+        threshold = 2.0 * np.sqrt(2.0) * np.sin(0.25)
+    out = np.empty(d * d); w = np.empty(max(n, 1)); it = C.c_int()
+    _check(lib().dpgo_robust_rotation_average(d, n, rp, kp, float(threshold), int(max_iters), float(mu_step),
+                                              out.ctypes.data_as(_dp), w.ctypes.data_as(_dp), C.byref(it)))
+    return out.reshape(d, d), w[:n], it.value
 
 
 def chordal_initialization(d, n, p1, p2, R, t, kappa, tau):
@@ -991,6 +1105,25 @@ class Rbcd:
     def set_X(self, X):
         x, xp = _f64(to_dev_layout(X) if X.ndim == 2 else X)
         _check(lib().dpgo_rbcd_set_X(self.h, xp))
+
+    def set_trajectory(self, T, YLift, frames=None):
+        """Start from an SE(d) trajectory (dpgo_rbcd_set_trajectory): T d x (d+1) n (or its flat column-major
+        buffer), every pose in the frame of its agent's entry of `frames` (K x d x (d+1); Graph.distributed_init_ex's
+        outputs) or, with frames None, already in one frame (a warm start from trajectory_into).  Lifted on the
+        device; the Nesterov state is (re)initialised as by set_X."""
+        d, r = self.graph.d, self.params.r
+        T = np.asarray(T, dtype=np.float64)
+        t, tp = _f64(to_dev_layout(T) if T.ndim == 2 else T)
+        if t.size != self.graph.n * d * (d + 1):
+            raise ValueError("T must be d x (d+1) n")
+        Y, Yp = _ylift_colmajor(YLift, r, d)
+        fp = None
+        if frames is not None:
+            F = np.asarray(frames, dtype=np.float64)
+            if F.shape != (self.num_agents, d, d + 1):
+                raise ValueError("frames must be num_agents x d x (d+1)")
+            f, fp = _f64(np.ascontiguousarray(F.transpose(0, 2, 1)).ravel())
+        _check(lib().dpgo_rbcd_set_trajectory(self.h, tp, Yp, fp))
 
     def get_X_into(self, Xflat):
         """Write owned poses into a global flat (device-layout) host array."""

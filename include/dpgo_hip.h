@@ -175,6 +175,18 @@ int dpgo_hip_round_se(int r, int d, int n, const double* X, const double* anchor
  * overlap X_dev */
 int dpgo_hip_round_se_dev(int r, int d, long long n, const double* X_dev, const double* anchor_dev,
                           double* T_dev, void* stream);
+/* The inverse of dpgo_hip_round_se: lift n SE(d) poses T (d x (d+1) n, column-major, [R_j | t_j] per pose) to rank r,
+ * each composed with a frame first: X_out (r x (d+1) n) = YLift [F_R R_j | F_R t_j + F_t] per pose, F = entry
+ * frame_of[j] of `frames` (nf x d x (d+1), column-major); YLift r x d column-major.  frames and frame_of both NULL:
+ * X_out = YLift T (T's entries only pass through the YLift product).  One streaming kernel.  DPGO_HIP_EINVAL for an
+ * unsupported (r, d), n <= 0, null T, YLift or X_out, exactly one of frames / frame_of null (or nf <= 0 with them),
+ * or a frame_of entry outside [0, nf). */
+int dpgo_hip_frame_lift(int r, int d, int n, const double* T, const double* YLift, const double* frames, int nf,
+                        const int* frame_of, double* X_out);
+/* the same on device pointers (YLift: host), queued on `stream` (hipStream_t or NULL), no synchronisation;
+ * X_out_dev must not overlap the inputs; frame_of_dev's entries are not checked */
+int dpgo_hip_frame_lift_dev(int r, int d, long long n, const double* T_dev, const double* YLift, const double* frames_dev,
+                            int nf, const int* frame_of_dev, double* X_out_dev, void* stream);
 
 /* ---- optimisation (QuadraticOptimizer::optimize, src/QuadraticOptimizer.cpp:34-149) -----*/
 /* Runs every agent of the handle; results[num_agents].  agent_enabled (optional, device or

@@ -68,12 +68,61 @@ int dpgo_graph_chordal_init_gpu(dpgo_graph g, int r, const double* YLift_colmajo
  * first pose -- the unconstrained rotation relaxation shrinks with graph distance from the anchor)
  * then initializeInGlobalFrame (:369-432): agents join the frame of the agent holding pose 0 in
  * breadth-first order, each by the L2 average over its shared loop closures with agents already in
- * the frame (the reference averages with GNC-TLS; identical on outlier-free data).  use_gpu: the
+ * the frame (the reference averages with GNC-TLS; identical on outlier-free data: with outlier loop closures
+ * use dpgo_graph_distributed_init_ex and DPGO_ALIGN_ROBUST_TWO_STAGE below).  use_gpu: the
  * block-diagonal chordal systems by Jacobi-PCG on the device (rtol, max_iters), else host Cholesky.
  * X_out = YLift * T (r x (d+1) n, column-major). */
 int dpgo_graph_distributed_init(dpgo_graph g, int num_agents, const int* agent_of_pose, int r,
                                 const double* YLift_colmajor, int use_gpu, double rtol, int max_iters, double* X_out,
                                 int* iters, double* relres);
+/* robustSingleRotationAveraging (src/DPGO_utils.cpp:582-644), host-only: GNC-TLS over the chordal mean of n rotations
+ * (R row-major d*d per item; kappa NULL = all ones).  The initial estimate is the L2 chordal mean projected to SO(d);
+ * mu_0 = min(c^2 / (2 max r^2 - c^2), 1e-5) with c = threshold and r_i^2 = kappa_i |R_opt - R_i|_F^2, and GNC is
+ * skipped when mu_0 <= 0; per iteration the kappa .* w weighted mean is solved, the weights follow RobustCost::weight
+ * for GNC_TLS (src/DPGO_robust.cpp:49-61), the loop stops when every weight is within 1e-8 of 0 or 1, else
+ * mu <- mu_step mu (at most max_iters iterations; the reference: 1000 and 1.4).  R_opt (row-major) is the estimate
+ * solved with the weights of the iteration BEFORE the final reweighting, as in the reference: converged outliers
+ * leave a small trace in it.  weights[n]: the final weights (inliers: > 1 - 1e-8); iters (may be NULL): GNC iterations
+ * run.  DPGO_HIP_EINVAL for n <= 0, d not 2 or 3, null R / R_opt / weights, or an item that is not a rotation to 1e-8
+ * (determinant and |R^T R - I|_F; the reference asserts this). */
+int dpgo_robust_rotation_average(int d, int n, const double* R, const double* kappa, double threshold, int max_iters,
+                                 double mu_step, double* R_opt, double* weights, int* iters);
+/* The multi-robot initialisation with the reference's choices under a robust cost, as per-agent local trajectories
+ * plus one frame per agent (dpgo_rbcd_set_trajectory takes exactly these; dpgo_hip_frame_lift lifts them). */
+#define DPGO_LOCAL_CHORDAL 0  /* chordal on the agent's private graph (the L2 cost's localInitialization) */
+#define DPGO_LOCAL_ODOMETRY 1 /* odometryInitialization: what localInitialization does under any robust cost */
+#define DPGO_ALIGN_L2 0               /* dpgo_graph_distributed_init's average over every shared closure */
+#define DPGO_ALIGN_ROBUST_TWO_STAGE 1 /* computeRobustNeighborTransformTwoStage (src/PGOAgent.cpp:290-331) */
+typedef struct {
+  int local_init;            /* DPGO_LOCAL_* (default CHORDAL) */
+  int align;                 /* DPGO_ALIGN_* (default L2) */
+  double max_rotation_error; /* GNC-TLS threshold, chordal: 2 sqrt(2) sin(0.25) = angular2ChordalSO3(0.5), ~30 deg */
+  int gnc_max_iters;         /* 1000 */
+  double gnc_mu_step;        /* 1.4 */
+  int use_gpu;               /* chordal solves by Jacobi-PCG on the device (default 0: host Cholesky) */
+  double rtol;               /* 1e-12 (use_gpu) */
+  int max_iters;             /* 20000 (use_gpu) */
+} dpgo_init_params;
+void dpgo_default_init_params(dpgo_init_params* p);
+/* LOCAL_ODOMETRY: each agent composes its odometry edges (both poses in the agent at consecutive local indices,
+ * dpgo_rbcd_weight_owner's rule) from its first pose = identity; DPGO_HIP_EINVAL naming the agent when they do not
+ * reach all of its poses (contiguous pose ranges, as in MultiRobotExample, are the supported partitions; the grid's
+ * sub-cubes also qualify, the snake order within a sub-cube being a path of lattice neighbours).
+ * ALIGN_ROBUST_TWO_STAGE: breadth-first from the agent holding pose 0, neighbours in ascending id; a new agent A is
+ * aligned to the single agent being dequeued (the reference's one neighborID): per shared closure with it the
+ * candidate frame is computeNeighborTransform's (:250-288), W_A-pose T_local(A-pose)^-1 with W_A-pose =
+ * W_parent-pose T_e (T_e^-1 for an edge leaving A); the rotation is dpgo_robust_rotation_average of the candidates
+ * (unit kappa, max_rotation_error), the translation the plain mean of the inlier candidates' translations.  An empty
+ * inlier set skips the pair and A waits for another aligned neighbour; DPGO_HIP_EINVAL if an agent is never aligned.
+ * ALIGN_L2 with LOCAL_CHORDAL: frame o local is dpgo_graph_distributed_init's trajectory, bitwise.
+ * Outputs: T_local d x (d+1) n column-major (each agent in its own frame); frames num_agents x d x (d+1) column-major
+ * (identity for the root); parent[num_agents] (-1 for the root); candidates / inliers [num_agents] (0 for the root);
+ * edge_inlier[m] (may be NULL): 1 an inlier candidate, 0 a rejected one, 255 not used as a candidate; iters / relres
+ * (may be NULL): the chordal solves' PCG iterations and largest relative residual (0 otherwise). */
+int dpgo_graph_distributed_init_ex(dpgo_graph g, int num_agents, const int* agent_of_pose,
+                                   const dpgo_init_params* params, double* T_local, double* frames, int* parent,
+                                   int* candidates, int* inliers, unsigned char* edge_inlier, int* iters,
+                                   double* relres);
 /* Grid graphs: agent = sub-cube (x/s, y/s, z/s), s = k / A; id = ax + A (ay + A az). */
 /* Certified optimality gap of an iterate X (r x (d+1) n, column-major, e.g. the engine's
  * dpgo_rbcd_get_X gathered over ranks) for the whole graph's central Q (unit weights): lambda_min of
@@ -159,6 +208,13 @@ int dpgo_rbcd_exchange_counts(dpgo_rbcd e, long long* send_counts, long long* re
 int dpgo_rbcd_set_X(dpgo_rbcd e, const double* X_global);
 /* write the owned poses into a global host array (other poses untouched) */
 int dpgo_rbcd_get_X(dpgo_rbcd e, double* X_global);
+/* The read-in that matches dpgo_rbcd_get_trajectory: start from an SE(d) trajectory.  T_global: d x (d+1) n
+ * column-major host array, every pose in the frame of its agent's entry of `frames` (num_agents x d x (d+1)
+ * column-major, dpgo_graph_distributed_init_ex's outputs), or already in one common frame with frames = NULL (an
+ * earlier dpgo_rbcd_get_trajectory, any other SE(d) guess).  Only the owned poses' d x (d+1) blocks cross to the
+ * device; there X = YLift [F_R R_j | F_R t_j + F_t] per pose (dpgo_hip_frame_lift_dev on the engine's stream; YLift
+ * r x d column-major), then the Nesterov state is (re)initialised exactly as by dpgo_rbcd_set_X.  Synchronises. */
+int dpgo_rbcd_set_trajectory(dpgo_rbcd e, const double* T_global, const double* YLift_colmajor, const double* frames);
 /* ---- solution readout: SE(d) trajectory and loop-closure weights ---------------------------
  * lifted pose of global pose `pose` (r x (d+1), column-major) if this rank owns it: *owned = 1 and
  * anchor written; else *owned = 0 and anchor untouched.  Synchronises.  (PGOAgent::setGlobalAnchor takes
