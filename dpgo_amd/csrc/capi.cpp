@@ -7,22 +7,15 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <map>
-#include <new>
-#include <stdexcept>
-#include <mutex>
 #include <string>
-#include <thread>
-#include <type_traits>
 #include <vector>
 
-#include "chol_internal.h"
 #include "graph_internal.h"
 #include "problem_internal.h"
 
@@ -119,11 +112,6 @@ dpgo::QView qview(dpgo_hip_problem h) {
   return dpgo::QView{h->rowptr.p, h->col.p, h->blocks.p, h->inc_ptr.p, h->inc.p, unit ? h->rec_unit.p : h->rec.p,
                      unit ? h->diag_unit.p : h->diag.p, h->rec_first.p, h->sv_ptr.p, h->sv_ids.p, h->inc_sv.p, h->fmt,
                      h->tuning};
-}
-
-int check_handle(dpgo_hip_problem h) {
-  if (!h) return fail(DPGO_HIP_EINVAL, "null problem handle");
-  return DPGO_HIP_OK;
 }
 
 hipError_t pooled_event(dpgo_hip_problem h, hipEvent_t* e) {
@@ -382,7 +370,8 @@ int sync_q_edges(dpgo_hip_problem h) {
   HIP_TRY(hipMemcpyAsync(h->inc.p, inc.data(), sizeof(int2) * inc.size(), hipMemcpyHostToDevice, h->stream));
   HIP_TRY(hipMemcpyAsync(h->rec.p, rec.data(), sizeof(double) * rec.size(), hipMemcpyHostToDevice, h->stream));
   h->h_inc_ptr = deg;  // the device factorisation's assembly tables (sync_chol) index these incidences
-  h->h_inc = inc;
+  h->h_inc.resize(inc.size());
+  for (size_t k = 0; k < inc.size(); ++k) h->h_inc[k] = {inc[k].x, inc[k].y};
   if (!diag.empty())
     HIP_TRY(hipMemcpyAsync(h->diag.p, diag.data(), sizeof(double) * diag.size(), hipMemcpyHostToDevice, h->stream));
   h->fmt = dpgo::QFMT_EDGES;
@@ -396,8 +385,8 @@ int sync_q_edges(dpgo_hip_problem h) {
 // block-Jacobi inverses (QuadraticProblem::setQ, src/QuadraticProblem.cpp:31-42).
 int sync_q(dpgo_hip_problem h) {
   if (!h->q_dirty) return DPGO_HIP_OK;
-  h->chol_state = 0;  // the exact preconditioner follows Q (setQ refactorises, :37-41)
-  h->sn_sym_ready = false;  // a new Q may have a new pattern
+  h->ex.state = 0;  // the exact preconditioner follows Q (setQ refactorises, :37-41)
+  h->ex.sym_ready = false;  // a new Q may have a new pattern
   const int f0 = h->q_fmt[0];
   for (int a = 1; a < h->K; ++a)
     if (h->q_fmt[a] != f0) return fail(DPGO_HIP_ESTATE, "agents of one handle mix BSR and edge-stream Q");
@@ -438,14 +427,10 @@ int sync_q(dpgo_hip_problem h) {
   return DPGO_HIP_OK;
 }
 
-// ---------------------------------------------------------------------------------------------
-// Exact preconditioner: the reference factorises P = Q + 0.1 I with CHOLMOD in
-// setQ (src/QuadraticProblem.cpp:37-41).  Here the factor is built on the host the first time the
-// EXACT mode is used after a setQ, per agent (agents are independent blocks, factorised in parallel
-// host threads), as nested-dissection supernodes (chol.cpp), and uploaded as dense panels plus one
-// work list per tree level shared by the batch (level l of every agent runs in one launch per sweep).
-constexpr long kMaxCholDoubles = 3L << 30;  // 24 GiB of panels per handle
+}  // namespace
 
+namespace dpgo {
+// one agent's Q as block-sparse rows (the exact preconditioner's host factorisation and symbolic analysis, exact.cpp)
 void agent_bsr(dpgo_hip_problem h, int a, HostBSR& out) {
   if (h->q_fmt[a] == dpgo::QFMT_BSR) {
     out = h->q_agent[a];
@@ -472,692 +457,9 @@ void agent_bsr(dpgo_hip_problem h, int a, HostBSR& out) {
   }
   out = std::move(B.out);
 }
+}  // namespace dpgo
 
-// host threads for the per-agent factorisations: DPGO_CHOL_THREADS, else OMP_NUM_THREADS (the GPU box
-// sets it to the per-GPU host share), else the hardware count, at most 16
-int chol_threads(int K) {
-  int t = 0;
-  for (const char* var : {"DPGO_CHOL_THREADS", "OMP_NUM_THREADS"})
-    if (const char* s = std::getenv(var)) {
-      t = std::atoi(s);
-      if (t > 0) break;
-    }
-  if (t <= 0) t = std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
-  return std::max(1, std::min(t, K));
-}
-
-// Events created for one scope and destroyed on every exit from it (an early HIP_TRY return included)
-struct ScopedEvents {
-  std::vector<hipEvent_t> ev;
-  explicit ScopedEvents(size_t n) : ev(n, nullptr) {}
-  ~ScopedEvents() {
-    for (auto e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
-  hipError_t create() {
-    for (auto& e : ev)
-      if (!e) {
-        const hipError_t r = hipEventCreate(&e);
-        if (r != hipSuccess) return r;
-      }
-    return hipSuccess;
-  }
-};
-
-// The last device factorisation's time (fac_ev pair): resolved when it is asked for, so a refactorisation inside
-// the solve loop never waits for the GPU
-int resolve_factor_ms(dpgo_hip_problem h) {
-  if (!h->chol_factor_pending) return DPGO_HIP_OK;
-  HIP_TRY(hipEventSynchronize(h->fac_ev[1]));
-  float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, h->fac_ev[0], h->fac_ev[1]));
-  h->chol_factor_ms = ms;
-  h->chol_factor_pending = false;
-  return DPGO_HIP_OK;
-}
-
-// DPGO_SN_COMPACT=0: the sweeps read every supernode's 64 x 64 tiles (no compact copy of the narrow ones), for A/B
-bool sn_compact_on() {
-  const char* e = std::getenv("DPGO_SN_COMPACT");
-  return !(e && e[0] == '0');
-}
-
-// the sweeps read their items' records (SnView::desc); DPGO_SN_DESC=0: the per-node arrays (A/B)
-bool sn_desc_on() {
-  const char* e = std::getenv("DPGO_SN_DESC");
-  return !(e && e[0] == '0');
-}
-
-// The narrow supernodes' compact panels from the freshly factorised tiles (stream-ordered after the factor)
-int compact_panels(dpgo_hip_problem h) {
-  if (!h->sn_compact || h->sn_citems_n == 0) return DPGO_HIP_OK;
-  HIP_TRY(dpgo::launch_sn_compact(h->b, h->sn_panel.p, h->sn_panel_off.p, h->sn_s.p, h->sn_t.p, h->sn_cpanel_off.p,
-                                  h->sn_cpanel.p, h->sn_citems.p, h->sn_citems_n, h->stream));
-  return DPGO_HIP_OK;
-}
-
-// The device numeric factorisation: k_sn_factor level by level (deepest first) over the symbolic structure and
-// the current edge-stream Q.  A non-positive pivot marks its agent in fac_not_pd ([K], reset here); that agent's
-// sweeps are skipped and its preconditioner output is its input, unprojected -- the reference's fallback per
-// QuadraticProblem (src/QuadraticProblem.cpp:81-86), so the other agents of the batch keep their factors.  Nothing
-// here waits for the GPU: the flags are read on the device by the sweeps, and by the host only when asked
-// (dpgo_hip_exact_fallback_agents).
-int device_factor(dpgo_hip_problem h) {
-  const int maxd = static_cast<int>(h->fac_level_off.size()) - 2;
-  HIP_TRY(hipMemsetAsync(h->fac_not_pd.p, 0, sizeof(int) * h->K, h->stream));
-  if (dpgo::poison_enabled()) {  // debug: the frontal matrices and panels as nothing-written NaN before each factor
-    for (auto& F : h->fac_F) HIP_TRY(dpgo::poison_fill(F.p, sizeof(double) * F.n, h->stream));
-    HIP_TRY(dpgo::poison_fill(h->sn_panel.p, sizeof(double) * h->chol_doubles, h->stream));
-  }
-  for (auto& ev : h->fac_ev)
-    if (!ev) HIP_TRY(hipEventCreate(&ev));  // owned by the handle: no leak on an early error return
-  hipEvent_t e0 = h->fac_ev[0], e1 = h->fac_ev[1];
-  HIP_TRY(hipEventRecord(e0, h->stream));
-  const bool verbose = std::getenv("DPGO_VERBOSE_CHOL") != nullptr;
-  ScopedEvents lev(verbose ? maxd + 2 : 0);
-  HIP_TRY(lev.create());
-  for (int dep = maxd; dep >= 0; --dep) {
-    const int n0 = h->fac_level_off[dep], n1 = h->fac_level_off[dep + 1];
-    dpgo::SnFactorView v{h->fac_nodes.p + n0, h->sn_s.p, h->sn_t.p, h->fac_off.p, h->sn_panel_off.p, h->sn_poses_off.p,
-                         h->sn_poses.p, h->fac_ch_off.p, h->fac_ch.p, h->fac_tp_off.p, h->fac_tp.p, h->fac_ent_off.p,
-                         h->fac_ent.p, h->fac_src.p, h->rec.p, h->diag.p, 0.1, h->fac_F[dep & 1].p,
-                         h->fac_F[(dep + 1) & 1].p, h->sn_panel.p, h->sn_node_agent.p, h->fac_not_pd.p};
-    if (verbose) HIP_TRY(hipEventRecord(lev.ev[dep + 1], h->stream));
-    if (dep < static_cast<int>(h->fac_seq.size()) && !h->fac_seq[dep].empty()) {
-      for (const auto& fl : h->fac_seq[dep])
-        HIP_TRY(dpgo::launch_sn_factor_tiled(h->b, v, fl.kind, fl.param, h->fac_titems.p + fl.off, fl.count,
-                                             h->stream));
-    } else {
-      HIP_TRY(dpgo::launch_sn_factor(h->b, v, n1 - n0, h->stream));
-    }
-  }
-  if (verbose) HIP_TRY(hipEventRecord(lev.ev[0], h->stream));
-  HIP_TRY(hipEventRecord(e1, h->stream));
-  DPGO_TRY(compact_panels(h));  // after the factor's timing window: part of the sweeps' data, not the factorisation
-  h->chol_factor_count += 1;
-  h->chol_factor_pending = true;
-  h->chol_state = 1;
-  if (verbose) {
-    DPGO_TRY(resolve_factor_ms(h));
-    std::fprintf(stderr, "[dpgo_hip] exact preconditioner: device factorisation %.2f ms; per level (depth: nodes ms):",
-                 h->chol_factor_ms);
-    for (int dep = maxd; dep >= 0; --dep) {
-      float lm = 0.f;
-      HIP_TRY(hipEventElapsedTime(&lm, lev.ev[dep + 1], lev.ev[dep]));
-      std::fprintf(stderr, " %d:%d %.1f", dep, h->fac_level_off[dep + 1] - h->fac_level_off[dep], static_cast<double>(lm));
-    }
-    std::fprintf(stderr, "\n");
-  }
-  return DPGO_HIP_OK;
-}
-
-// DPGO_SN_FWD_SMALL=0: every forward item through k_sn_fwd (round 4's one kernel per level), for A/B runs
-bool sn_fwd_small_on() {
-  const char* e = std::getenv("DPGO_SN_FWD_SMALL");
-  return !(e && e[0] == '0');
-}
-
-
-int sync_chol(dpgo_hip_problem h) {
-  if (h->chol_state != 0) return DPGO_HIP_OK;
-  bool edges = true;
-  for (int a = 0; a < h->K; ++a) edges = edges && h->q_fmt[a] == dpgo::QFMT_EDGES;
-  const bool device = edges && h->tuning[dpgo::TUNE_DEVICE_CHOL] > 0;
-  if (device && h->sn_sym_ready) return device_factor(h);  // same pattern: only the numeric half again
-  if (!device && h->host_weights_stale) {  // weights changed on the device: bring the host measurement copy up to date
-    std::vector<double> w(std::max<long>(h->num_edges, 1));
-    HIP_TRY(hipMemcpyAsync(w.data(), h->w_dev_last, sizeof(double) * h->num_edges, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    long eg = 0;
-    for (int a = 0; a < h->K; ++a) {
-      HostEdges& E = h->e_agent[a];
-      for (size_t e = 0; e < E.p1.size(); ++e, ++eg) {
-        E.kw[e] = w[eg] * E.kappa0[e];
-        E.tw[e] = w[eg] * E.tau0[e];
-      }
-    }
-    h->host_weights_stale = false;
-  }
-  const int b = h->b, r = h->r, K = h->K;
-  // ---- per-agent factor structure (device: symbolic only; host: the whole factorisation), host threads
-  std::vector<dpgo::SupernodalFactor> Fs(K);
-  std::vector<std::string> errs(K);
-  std::vector<int> rcs(K, 0);
-  {
-    std::atomic<int> next{0}, done{0};
-    const auto t0 = std::chrono::steady_clock::now();
-    std::mutex log_mu;
-    auto work = [&]() {
-      for (int a = next++; a < K; a = next++) {
-        try {
-          HostBSR Q;
-          agent_bsr(h, a, Q);
-          rcs[a] = device ? dpgo::supernodal_symbolic(h->n_agent[a], b, Q.rowptr, Q.col, kMaxCholDoubles, Fs[a], errs[a])
-                          : dpgo::supernodal_cholesky(h->n_agent[a], b, Q.rowptr, Q.col, Q.blocks, 0.1, kMaxCholDoubles,
-                                                      Fs[a], errs[a]);
-        } catch (const std::bad_alloc&) {
-          rcs[a] = -2;
-          errs[a] = "exact preconditioner: out of host memory in the factorisation";
-        } catch (const std::exception& ex) {
-          rcs[a] = -1;
-          errs[a] = std::string("exact preconditioner: ") + ex.what();
-        }
-        // a long factorisation reports progress (a silent process looks hung to a supervisor)
-        const int k = ++done;
-        const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        if (sec > 5.0) {
-          std::lock_guard<std::mutex> lk(log_mu);
-          std::fprintf(stderr, "[dpgo_hip] exact preconditioner: %d / %d agents factorised (%.1f s)\n", k, K, sec);
-        }
-      }
-    };
-    const int nt = chol_threads(K);
-    std::vector<std::thread> pool;
-    for (int i = 1; i < nt; ++i) pool.emplace_back(work);
-    work();
-    for (auto& t : pool) t.join();
-  }
-  long total = 0;
-  std::vector<int> host_ident(K, 0);  // host factorisation: agents whose Q + 0.1 I met a non-positive pivot
-  for (int a = 0; a < K; ++a) {
-    if (rcs[a] != 0) {
-      if (errs[a].find("positive definite") == std::string::npos)
-        return fail(rcs[a] == -2 ? DPGO_HIP_ENOMEM : DPGO_HIP_EINVAL, errs[a]);
-      // src/QuadraticProblem.cpp:81-86, per QuadraticProblem: this agent's solves fail -> "Preconditioner failed",
-      // out = in; the batch's other agents keep their factors.  The agent keeps its symbolic structure (its
-      // supernodes are skipped by the sweeps, so its panels are never read).
-      std::printf("[dpgo_hip] Preconditioner failed (agent %d: %s); using the identity for it.\n", a, errs[a].c_str());
-      host_ident[a] = 1;
-      HostBSR Q;
-      agent_bsr(h, a, Q);
-      std::string e2;
-      Fs[a] = dpgo::SupernodalFactor();
-      if (dpgo::supernodal_symbolic(h->n_agent[a], b, Q.rowptr, Q.col, kMaxCholDoubles, Fs[a], e2) != 0)
-        return fail(DPGO_HIP_EINVAL, e2);
-    }
-    total += Fs[a].panel_doubles;
-  }
-  if (total > kMaxCholDoubles)
-    return fail(DPGO_HIP_EINVAL, "exact preconditioner: the supernodal panels of the batch would exceed 24 GiB "
-                                 "(use DPGO_PRECON_BLOCK_JACOBI for this size)");
-  if (std::getenv("DPGO_VERBOSE_CHOL"))
-    std::fprintf(stderr, "[dpgo_hip] exact preconditioner: %d agents, %.3f GiB of supernodal panels\n", K,
-                 8.0 * static_cast<double>(total) / (1024.0 * 1024.0 * 1024.0));
-  // ---- the batch's node list (agents in order, each in postorder), work lists per tree level
-  std::vector<int> base(K + 1, 0);
-  for (int a = 0; a < K; ++a) base[a + 1] = base[a] + static_cast<int>(Fs[a].nodes.size());
-  const int nn = base[K];
-  std::vector<long> panel_off(nn), f_off(nn), u_off(nn);
-  std::vector<int> s_(nn), t_(nn), poses_off(nn), poses, cpos_off(nn), cpos;
-  std::vector<int2> contrib;
-  int maxd = 0;
-  long fo = 0, uo = 0, po = 0;
-  // DPGO_PANEL_GUARD=1 (debug runs): a one-tile gap of all-ones bytes (NaN) after EVERY supernode's panel and 1 Mi
-  // doubles after the last; exact_precond checks every gap after each application (a write past a node's panel into
-  // the next changes a gap), and a gap value read into a product turns the result NaN (a read past the panel)
-  static const bool guard = std::getenv("DPGO_PANEL_GUARD") != nullptr;
-  const long kGap = guard ? static_cast<long>(dpgo::kSnTile) * dpgo::kSnTile : 0;
-  std::vector<std::pair<long, long>> guards;
-  double flops = 0.0, inv_flops = 0.0;
-  for (int a = 0; a < K; ++a) {
-    const auto& nodes = Fs[a].nodes;
-    const long off = h->pose_off[a];
-    for (size_t x = 0; x < nodes.size(); ++x) {
-      const int g = base[a] + static_cast<int>(x);
-      const dpgo::SnNode& nd = nodes[x];
-      const int s = static_cast<int>(nd.S.size()), t = static_cast<int>(nd.R.size());
-      s_[g] = s;
-      t_[g] = t;
-      {  // scalars: POTRF of the frontal S block, TRSM of the R rows, the update of the R x R frontal block
-        const double ss = static_cast<double>(s) * b, ts = static_cast<double>(t) * b;
-        flops += ss * ss * ss / 3.0 + ss * ss * ts + ss * ts * ts;
-        inv_flops += ss * ss * ss / 3.0 + ss * ss * ts;
-      }
-      panel_off[g] = po;
-      po += dpgo::sn_panel_tiles(s * b, t * b) * dpgo::kSnTile * dpgo::kSnTile;
-      if (guard) {
-        guards.emplace_back(po, kGap);
-        po += kGap;
-      }
-      f_off[g] = fo;
-      fo += static_cast<long>(dpgo::sn_pad(s * b) + dpgo::sn_pad(t * b)) * r;
-      u_off[g] = uo;
-      uo += static_cast<long>(t) * b * r;
-      poses_off[g] = static_cast<int>(poses.size());
-      for (int v : nd.S) poses.push_back(static_cast<int>(off + v));
-      for (int v : nd.R) poses.push_back(static_cast<int>(off + v));
-      // per frontal position, its children's contributions in child order
-      std::vector<std::vector<int2>> at(s + t);
-      for (int c : nd.children) {
-        const dpgo::SnNode& ch = nodes[c];
-        for (size_t i = 0; i < ch.R.size(); ++i) at[ch.to_parent[i]].push_back(make_int2(base[a] + c, static_cast<int>(i)));
-      }
-      cpos_off[g] = static_cast<int>(cpos.size());
-      cpos.push_back(static_cast<int>(contrib.size()));
-      for (int p = 0; p < s + t; ++p) {
-        contrib.insert(contrib.end(), at[p].begin(), at[p].end());
-        cpos.push_back(static_cast<int>(contrib.size()));
-      }
-      maxd = std::max(maxd, nd.depth);
-    }
-  }
-  std::vector<int2> items;
-  std::vector<char> level_small;  // per depth: every node narrow (its forward items through k_sn_fwd_small)
-  h->sn_levels.assign(maxd + 1, {});
-  for (int dep = 0; dep <= maxd; ++dep) {
-    auto& L = h->sn_levels[dep];
-    L.asm0 = static_cast<int>(items.size());
-    for (int a = 0; a < K; ++a)
-      for (size_t x = 0; x < Fs[a].nodes.size(); ++x)
-        if (Fs[a].nodes[x].depth == dep) {
-          const int g = base[a] + static_cast<int>(x);
-          const int rows = dpgo::sn_pad(s_[g] * b) + dpgo::sn_pad(t_[g] * b);
-          for (int blk = 0; blk * dpgo::kThreads < rows; ++blk) items.push_back(make_int2(g, blk));
-        }
-    L.asm_n = static_cast<int>(items.size()) - L.asm0;
-    // The sweeps' work items, nodes in order: forward one per row tile I of a node (it streams the row's
-    // min(I + 1, ns) tiles) -- on a level of narrow nodes only (ns <= kSnSmallNs) through k_sn_fwd_small, else k_sn_fwd;
-    // backward one per column tile J (nI - J tiles).  (Runs of a narrow node's row tiles in one workgroup measured
-    // slower: 3.76 vs 3.48 ms per C5 forward sweep.)
-    // (a level with both kinds runs every item through k_sn_fwd: a second launch there cost more than the narrow
-    // nodes' items gained, profiles/r05k_levels.txt)
-    bool small = sn_fwd_small_on();
-    level_small.resize(maxd + 1, 0);
-    for (int a = 0; a < K && small; ++a)
-      for (size_t x = 0; x < Fs[a].nodes.size(); ++x)
-        if (Fs[a].nodes[x].depth == dep && dpgo::sn_pad(s_[base[a] + static_cast<int>(x)] * b) / dpgo::kSnTile > dpgo::kSnSmallNs) {
-          small = false;
-          break;
-        }
-    for (int pass = 0; pass < 2; ++pass) {
-      (pass == 0 ? L.fws0 : L.fwd0) = static_cast<int>(items.size());
-      for (int a = 0; a < K; ++a)
-        for (size_t x = 0; x < Fs[a].nodes.size(); ++x)
-          if (Fs[a].nodes[x].depth == dep) {
-            const int g = base[a] + static_cast<int>(x);
-            const int ns = dpgo::sn_pad(s_[g] * b) / dpgo::kSnTile;
-            const bool narrow = small && ns <= dpgo::kSnSmallNs;
-            if (narrow != (pass == 0)) continue;
-            const int nI = (dpgo::sn_pad(s_[g] * b) + dpgo::sn_pad(t_[g] * b)) / dpgo::kSnTile;
-            for (int I = 0; I < nI; ++I) items.push_back(make_int2(g, I));
-          }
-      if (pass == 0) L.fws_n = static_cast<int>(items.size()) - L.fws0;
-    }
-    level_small[dep] = small ? 1 : 0;
-    L.fwd_n = static_cast<int>(items.size()) - L.fwd0;
-    L.bwd0 = static_cast<int>(items.size());
-    for (int a = 0; a < K; ++a)
-      for (size_t x = 0; x < Fs[a].nodes.size(); ++x)
-        if (Fs[a].nodes[x].depth == dep) {
-          const int g = base[a] + static_cast<int>(x);
-          const int nJ = dpgo::sn_pad(s_[g] * b) / dpgo::kSnTile;
-          for (int J = 0; J < nJ; ++J) items.push_back(make_int2(g, J));
-        }
-    L.bwd_n = static_cast<int>(items.size()) - L.bwd0;
-  }
-  // ---- upload
-  // every upload is ordered on h->stream (the handle's stream is non-blocking: a copy on the null stream is not
-  // ordered before the sweeps and factor kernels queued after it); the host vectors live until the stream
-  // synchronisation at the end of this function (both paths: device_factor itself never waits)
-  auto up = [&](auto& d, const auto& v) -> int {
-    using T = typename std::decay_t<decltype(v)>::value_type;
-    HIP_TRY(d.ensure(std::max<size_t>(v.size(), 1)));
-    if (!v.empty()) HIP_TRY(hipMemcpyAsync(d.p, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice, h->stream));
-    return DPGO_HIP_OK;
-  };
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  constexpr long kGuard = 1L << 20;
-  HIP_TRY(h->sn_panel.ensure(std::max<long>(po, 1) + (guard ? kGuard : 0)));
-  if (guard) {  // the whole buffer NaN first: the panels are written over it, the gaps keep it
-    HIP_TRY(hipMemsetAsync(h->sn_panel.p, 0xFF, sizeof(double) * (std::max<long>(po, 1) + kGuard), h->stream));
-    guards.emplace_back(std::max<long>(po, 1), kGuard);
-  }
-  h->sn_guards = guards;
-  if (device && dpgo::poison_enabled()) HIP_TRY(dpgo::poison_fill(h->sn_panel.p, sizeof(double) * po, h->stream));
-  if (!device) {
-    // The host factor's panels go up through a pinned staging buffer, one agent at a time: one DMA per node from
-    // pinned memory instead of the runtime's pageable-copy path (DPGO_PANEL_UPLOAD_DIRECT=1: the pageable copies).
-    const char* dv = std::getenv("DPGO_PANEL_UPLOAD_DIRECT");
-    const bool direct = dv != nullptr && std::atoi(dv) != 0;
-    size_t stage_n = 0;
-    for (int a = 0; a < K && !direct; ++a) {
-      size_t na = 0;
-      for (const auto& nd : Fs[a].nodes) na += nd.panel.size();
-      stage_n = std::max(stage_n, na);
-    }
-    double* stage = nullptr;
-    if (stage_n > 0 && hipHostMalloc(reinterpret_cast<void**>(&stage), sizeof(double) * stage_n) != hipSuccess)
-      return fail(DPGO_HIP_ENOMEM, "pinned staging buffer for the panels");
-    struct StageFree {
-      double* p;
-      ~StageFree() {
-        if (p) (void)hipHostFree(p);
-      }
-    } stage_free{stage};
-    for (int a = 0; a < K; ++a) {
-      size_t so = 0;
-      for (size_t x = 0; x < Fs[a].nodes.size(); ++x) {
-        const auto& P = Fs[a].nodes[x].panel;
-        if (P.empty()) continue;
-        const double* src = P.data();
-        if (!direct) {
-          std::memcpy(stage + so, P.data(), sizeof(double) * P.size());
-          src = stage + so;
-          so += P.size();
-        }
-        HIP_TRY(hipMemcpyAsync(h->sn_panel.p + panel_off[base[a] + x], src, sizeof(double) * P.size(),
-                               hipMemcpyHostToDevice, h->stream));
-      }
-      HIP_TRY(hipStreamSynchronize(h->stream));  // then release the agent's host panels (and reuse the stage)
-      for (auto& nd : Fs[a].nodes) std::vector<double>().swap(nd.panel);
-    }
-  }
-  DPGO_TRY(up(h->sn_panel_off, panel_off));
-  DPGO_TRY(up(h->sn_f_off, f_off));
-  DPGO_TRY(up(h->sn_u_off, u_off));
-  DPGO_TRY(up(h->sn_s, s_));
-  DPGO_TRY(up(h->sn_t, t_));
-  DPGO_TRY(up(h->sn_poses_off, poses_off));
-  DPGO_TRY(up(h->sn_poses, poses));
-  DPGO_TRY(up(h->sn_cpos_off, cpos_off));
-  DPGO_TRY(up(h->sn_cpos, cpos));
-  DPGO_TRY(up(h->sn_contrib, contrib));
-  DPGO_TRY(up(h->sn_items, items));
-  std::vector<int> node_agent(base[K]);
-  for (int a = 0; a < K; ++a)
-    for (int g = base[a]; g < base[a + 1]; ++g) node_agent[g] = a;
-  DPGO_TRY(up(h->sn_node_agent, node_agent));
-  if (!device) DPGO_TRY(up(h->fac_not_pd, host_ident));
-  {  // narrow supernodes (<= kSnSmallNs S column tiles): a compact (s b + t b) x ld copy the sweeps read instead
-    h->sn_compact = sn_compact_on();
-    // (k_sn_bwd reads every narrow node compact; the forward sweep only through k_sn_fwd_small, i.e. on levels of
-    // narrow nodes only -- k_sn_fwd keeps to the tiles)
-    std::vector<long> coff(nn, -1);
-    std::vector<int2> citems;
-    long co = 0;
-    double fwd_bytes = 0.0, bwd_bytes = 0.0;
-    for (int a = 0; a < K; ++a)
-      for (size_t x = 0; x < Fs[a].nodes.size(); ++x) {
-        const int g = base[a] + static_cast<int>(x);
-        const int sb = s_[g] * b, tb = t_[g] * b;
-        const double tiles = 8.0 * static_cast<double>(dpgo::sn_panel_tiles(sb, tb) * dpgo::kSnTile * dpgo::kSnTile);
-        if (h->sn_compact && dpgo::sn_pad(sb) / dpgo::kSnTile <= dpgo::kSnSmallNs) {
-          coff[g] = co;
-          const long dbl = static_cast<long>(sb + tb) * dpgo::sn_compact_ld(sb);
-          co += (dbl + 15) / 16 * 16;  // 128-byte aligned nodes
-          bwd_bytes += 8.0 * static_cast<double>(dbl);
-          fwd_bytes += level_small[Fs[a].nodes[x].depth] ? 8.0 * static_cast<double>(dbl) : tiles;
-          for (int r0 = 0; r0 < sb + tb; r0 += dpgo::kSnTile) citems.push_back(make_int2(g, r0 / dpgo::kSnTile));
-        } else {
-          fwd_bytes += tiles;
-          bwd_bytes += tiles;
-        }
-      }
-    h->sn_sweep_bytes_fwd = fwd_bytes;
-    h->sn_sweep_bytes_bwd = bwd_bytes;
-    h->sn_citems_n = static_cast<int>(citems.size());
-    DPGO_TRY(up(h->sn_cpanel_off, coff));
-    DPGO_TRY(up(h->sn_citems, citems));
-    HIP_TRY(h->sn_cpanel.ensure(std::max<long>(co, 1)));
-    // every sweep item's record (k_sn_fwd, k_sn_fwd_small, k_sn_bwd read it in one load)
-    std::vector<dpgo::SnItem> desc(items.size());
-    for (size_t i = 0; i < items.size(); ++i) {
-      const int g = items[i].x;
-      dpgo::SnItem& d = desc[i];
-      d.node = g;
-      d.tile = items[i].y;
-      d.agent = node_agent[g];
-      d.s = s_[g];
-      d.t = t_[g];
-      d.pad = 0;
-      d.f_off = f_off[g];
-      d.u_off = u_off[g];
-      d.panel_off = panel_off[g];
-      d.cpanel_off = h->sn_compact ? coff[g] : -1;
-      d.poses_off = poses_off[g];
-    }
-    DPGO_TRY(up(h->sn_desc, desc));
-  }
-  HIP_TRY(h->sn_F.ensure(std::max<long>(fo, 1)));
-  HIP_TRY(h->sn_U.ensure(std::max<long>(uo, 1)));
-  h->chol_doubles = po;
-  h->sn_nodes = nn;
-  h->chol_flops = flops;
-  h->chol_inv_flops = inv_flops;
-  if (!device) {
-    DPGO_TRY(compact_panels(h));
-    HIP_TRY(hipStreamSynchronize(h->stream));  // the uploaded host tables die with this frame
-    h->chol_state = 1;
-    return DPGO_HIP_OK;
-  }
-  // ---- the device factorisation's tables: per tree level its nodes, per node its children, the positions of its R
-  // entries in its parent's frontal order, and the original entries of its S columns from the edge-stream Q
-  std::vector<int> fac_nodes, level_off(maxd + 2, 0), ch_off(nn + 1, 0), ch, tp_off(nn, 0), tp, ent_off(nn + 1, 0),
-      src;
-  std::vector<long> fac_off(nn, 0);
-  std::vector<dpgo::SnEntry> ent;
-  long level_size[2] = {0, 0};
-  for (int dep = 0; dep <= maxd; ++dep) {
-    level_off[dep] = static_cast<int>(fac_nodes.size());
-    long lo = 0;
-    for (int a = 0; a < K; ++a)
-      for (size_t x = 0; x < Fs[a].nodes.size(); ++x)
-        if (Fs[a].nodes[x].depth == dep) {
-          const int g = base[a] + static_cast<int>(x);
-          fac_nodes.push_back(g);
-          const long M = dpgo::sn_pad(s_[g] * b) + dpgo::sn_pad(t_[g] * b);
-          fac_off[g] = lo;
-          lo += M * M;
-        }
-    level_size[dep & 1] = std::max(level_size[dep & 1], lo);
-  }
-  level_off[maxd + 1] = static_cast<int>(fac_nodes.size());
-  std::vector<int> fpos;
-  for (int a = 0; a < K; ++a) {
-    const auto& nodes = Fs[a].nodes;
-    const long off = h->pose_off[a];
-    fpos.assign(h->n_agent[a], -1);
-    for (size_t x = 0; x < nodes.size(); ++x) {
-      const int g = base[a] + static_cast<int>(x);
-      const dpgo::SnNode& nd = nodes[x];
-      for (int c : nd.children) ch.push_back(base[a] + c);
-      ch_off[g + 1] = static_cast<int>(ch.size());
-      tp_off[g] = static_cast<int>(tp.size());
-      tp.insert(tp.end(), nd.to_parent.begin(), nd.to_parent.end());
-      const int s = static_cast<int>(nd.S.size());
-      for (int p = 0; p < s; ++p) fpos[nd.S[p]] = p;
-      for (size_t q = 0; q < nd.R.size(); ++q) fpos[nd.R[q]] = s + static_cast<int>(q);
-      for (int p = 0; p < s; ++p) {
-        ent.push_back(dpgo::SnEntry{p, p, 0, 0});  // the diagonal block (+ shift)
-        const long gv = off + nd.S[p];
-        // incidences of the column's pose (ascending edge id), grouped by the frontal row they land in
-        std::vector<std::pair<int, int>> rows;  // (q, code)
-        for (int k = h->h_inc_ptr[gv]; k < h->h_inc_ptr[gv + 1]; ++k) {
-          const int2 ie = h->h_inc[k];
-          const int q = fpos[ie.y - off];
-          if (q >= p) rows.emplace_back(q, ie.x);  // q < 0: eliminated below; q < p: the upper triangle
-        }
-        std::stable_sort(rows.begin(), rows.end(), [](const auto& x, const auto& y) { return x.first < y.first; });
-        for (size_t i = 0; i < rows.size();) {
-          size_t j = i;
-          const int s0 = static_cast<int>(src.size());
-          for (; j < rows.size() && rows[j].first == rows[i].first; ++j) src.push_back(rows[j].second);
-          ent.push_back(dpgo::SnEntry{rows[i].first, p, s0, static_cast<int>(src.size())});
-          i = j;
-        }
-      }
-      ent_off[g + 1] = static_cast<int>(ent.size());
-      for (int v : nd.S) fpos[v] = -1;
-      for (int v : nd.R) fpos[v] = -1;
-    }
-  }
-  // tile-parallel levels: every level by default (with the A strips in registers the tile kernels beat one workgroup
-  // per node at every depth: C5 151 -> 142 ms); DPGO_FAC_TILED_MAX_NODES / _MIN_TILES restrict them (0: never)
-  int tiled_max = 1 << 30, tiled_min_rows = 1;
-  if (const char* e = std::getenv("DPGO_FAC_TILED_MAX_NODES")) tiled_max = std::atoi(e);
-  if (const char* e = std::getenv("DPGO_FAC_TILED_MIN_TILES")) tiled_min_rows = std::atoi(e);  // tests: small graphs
-  std::vector<int2> titems;
-  h->fac_seq.assign(maxd + 1, {});
-  for (int dep = 0; dep <= maxd; ++dep) {
-    const int n0 = level_off[dep], n1 = level_off[dep + 1];
-    int max_nt = 0, max_ns = 0, max_ch = 0;
-    for (int x = n0; x < n1; ++x) {
-      const int g = fac_nodes[x];
-      const int Sp = dpgo::sn_pad(s_[g] * b), M = Sp + dpgo::sn_pad(t_[g] * b);
-      max_nt = std::max(max_nt, M / dpgo::kSnTile);
-      max_ns = std::max(max_ns, Sp / dpgo::kSnTile);
-      max_ch = std::max(max_ch, ch_off[g + 1] - ch_off[g]);
-    }
-    if (n1 - n0 > tiled_max || max_nt < tiled_min_rows) continue;
-    auto& seq = h->fac_seq[dep];
-    auto launch = [&](int kind, int param, const std::vector<int2>& it) {
-      if (it.empty()) return;
-      seq.push_back({kind, param, static_cast<int>(titems.size()), static_cast<int>(it.size())});
-      titems.insert(titems.end(), it.begin(), it.end());
-    };
-    std::vector<int2> it;
-    for (int phase = 0; phase < 2 + max_ch; ++phase) {  // assembly: zero, entries, children in order
-      it.clear();
-      for (int x = n0; x < n1; ++x) {
-        const int g = fac_nodes[x];
-        long n = 0;
-        if (phase == 0)
-          n = (dpgo::sn_pad(s_[g] * b) + dpgo::sn_pad(t_[g] * b) + dpgo::kSnTile - 1) / dpgo::kSnTile;
-        else if (phase == 1)
-          n = (ent_off[g + 1] - ent_off[g] + dpgo::kThreads - 1) / dpgo::kThreads;
-        else if (phase - 2 < ch_off[g + 1] - ch_off[g])
-          n = (static_cast<long>(t_[ch[ch_off[g] + phase - 2]]) * b + dpgo::kSnTile - 1) / dpgo::kSnTile;
-        for (int y = 0; y < n; ++y) it.push_back(make_int2(g, y));
-      }
-      launch(0, phase, it);
-    }
-    // right-looking over blocks of kBK columns: inside a block every K updates only the block's own columns
-    // (the next diagonal tiles and L_IK depend on them); the tiles right of the block take the block's kBK
-    // updates in one pass (kind 5: one load / store of F_IJ instead of kBK, the same MFMA order)
-    constexpr int kBK = 4;  // kSnfBlockK (kernels.hip)
-    for (int KB = 0; KB < max_ns; KB += kBK) {
-      for (int K = KB; K < std::min(KB + kBK, max_ns); ++K) {
-        std::vector<int2> dg, ts, up;
-        for (int x = n0; x < n1; ++x) {
-          const int g = fac_nodes[x];
-          const int ns = dpgo::sn_pad(s_[g] * b) / dpgo::kSnTile;
-          const int NT = ns + dpgo::sn_pad(t_[g] * b) / dpgo::kSnTile;
-          if (K >= ns) continue;
-          dg.push_back(make_int2(g, 0));
-          for (int I = K + 1; I < NT; ++I) {
-            ts.push_back(make_int2(g, I));
-            for (int J = K + 1; J <= std::min(I, KB + kBK - 1); ++J) up.push_back(make_int2(g, (I << 16) | J));
-          }
-        }
-        launch(1, K, dg);
-        launch(2, K, ts);
-        launch(3, K, up);
-      }
-      std::vector<int2> rest;
-      for (int x = n0; x < n1; ++x) {
-        const int g = fac_nodes[x];
-        const int ns = dpgo::sn_pad(s_[g] * b) / dpgo::kSnTile;
-        const int NT = ns + dpgo::sn_pad(t_[g] * b) / dpgo::kSnTile;
-        if (KB >= ns) continue;
-        for (int I = KB + kBK; I < NT; ++I)
-          for (int J = KB + kBK; J <= I; ++J) rest.push_back(make_int2(g, (I << 16) | J));
-      }
-      launch(5, KB, rest);
-    }
-    for (int J = max_ns - 1; J >= 0; --J) {
-      it.clear();
-      for (int x = n0; x < n1; ++x) {
-        const int g = fac_nodes[x];
-        const int ns = dpgo::sn_pad(s_[g] * b) / dpgo::kSnTile;
-        const int NT = ns + dpgo::sn_pad(t_[g] * b) / dpgo::kSnTile;
-        if (J >= ns) continue;
-        for (int I = J + 1; I < NT; ++I) it.push_back(make_int2(g, I));
-      }
-      launch(4, J, it);
-    }
-  }
-  DPGO_TRY(up(h->fac_titems, titems));
-  if (std::getenv("DPGO_VERBOSE_CHOL")) {
-    std::fprintf(stderr, "[dpgo_hip] exact preconditioner: device factorisation, %d levels, frontal buffers %.3f + %.3f GiB\n",
-                 maxd + 1, 8.0 * level_size[0] / (1 << 30), 8.0 * level_size[1] / (1 << 30));
-    std::fprintf(stderr, "[dpgo_hip] exact preconditioner: tile-parallel levels:");
-    for (int dep = 0; dep <= maxd; ++dep)
-      if (!h->fac_seq[dep].empty()) std::fprintf(stderr, " %d (%zu launches)", dep, h->fac_seq[dep].size());
-    std::fprintf(stderr, ", %zu items\n", titems.size());
-  }
-  h->fac_level_off = level_off;
-  DPGO_TRY(up(h->fac_nodes, fac_nodes));
-  DPGO_TRY(up(h->fac_off, fac_off));
-  DPGO_TRY(up(h->fac_ch_off, ch_off));
-  DPGO_TRY(up(h->fac_ch, ch));
-  DPGO_TRY(up(h->fac_tp_off, tp_off));
-  DPGO_TRY(up(h->fac_tp, tp));
-  DPGO_TRY(up(h->fac_ent_off, ent_off));
-  DPGO_TRY(up(h->fac_ent, ent));
-  DPGO_TRY(up(h->fac_src, src));
-  HIP_TRY(h->fac_not_pd.ensure(K));
-  for (int q = 0; q < 2; ++q) HIP_TRY(h->fac_F[q].ensure(std::max<long>(level_size[q], 1)));
-  h->sn_sym_ready = true;
-  // the uploaded host tables die with this frame: an asynchronous copy from pageable memory need not have read its
-  // source when the call returns.  Only after a symbolic rebuild; refactorisations (sn_sym_ready) never wait.
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  return device_factor(h);
-}
-
-// z = P_X(in (Q + 0.1 I)^-1) for every agent (QuadraticProblem::PreConditioner, :75-87): the forward sweep
-// up the supernodal trees into tA, the backward sweep down into tB (one launch per level and kernel), then
-// projection + partials <z, rref>, |rref|^2 (pass rref = in).  With a failed factorisation z = in,
-// unprojected, as the reference.  Agents that `flag` skips (k_precond_finish leaves their z untouched) are skipped
-// by the sweeps too: a tCG iteration streams only the panels of the agents still in tCG.
-int exact_precond(dpgo_hip_problem h, const double* in, double* z_out, double* delta_out, const double* X,
-                  const double* rref, double* partials, int flag) {
-  DPGO_TRY(sync_chol(h));
-  const double* zraw = in;
-  if (h->chol_state == 1) {
-    dpgo::SnView v{h->sn_panel.p, h->sn_panel_off.p, h->sn_s.p,    h->sn_t.p,    h->sn_poses_off.p,
-                   h->sn_poses.p, h->sn_f_off.p,     h->sn_u_off.p, h->sn_cpos_off.p, h->sn_cpos.p,
-                   h->sn_contrib.p, h->sn_F.p,       h->sn_U.p,    h->sn_node_agent.p, h->state.p, flag,
-                   h->fac_not_pd.p, h->sn_cpanel.p, h->sn_compact ? h->sn_cpanel_off.p : nullptr};
-    const int2* it = h->sn_items.p;
-    v.desc = sn_desc_on() ? h->sn_desc.p : nullptr;
-    v.items_base = it;
-    const int nl = static_cast<int>(h->sn_levels.size());
-    if (dpgo::poison_enabled())  // debug: frontal / update / sweep vectors as nothing-written NaN
-      for (auto* B : {&h->sn_F, &h->sn_U, &h->tA, &h->tB}) HIP_TRY(dpgo::poison_fill(B->p, sizeof(double) * B->n, h->stream));
-    for (int l = nl - 1; l >= 0; --l) {
-      const auto& L = h->sn_levels[l];
-      HIP_TRY(dpgo::launch_sn_assemble(h->r, h->b, v, it + L.asm0, L.asm_n, in, h->stream));
-      HIP_TRY(dpgo::launch_sn_fwd_small(h->r, h->b, v, it + L.fws0, L.fws_n, h->tA.p, h->stream));
-      HIP_TRY(dpgo::launch_sn_fwd(h->r, h->b, v, it + L.fwd0, L.fwd_n, h->tA.p, h->stream));
-    }
-    for (int l = 0; l < nl; ++l) {
-      const auto& L = h->sn_levels[l];
-      HIP_TRY(dpgo::launch_sn_bwd(h->r, h->b, v, it + L.bwd0, L.bwd_n, h->tA.p, h->tB.p, h->stream));
-    }
-    zraw = h->tB.p;
-    if (!h->sn_guards.empty()) {  // DPGO_PANEL_GUARD: every gap between the panels, and the one after them, untouched?
-      HIP_TRY(hipStreamSynchronize(h->stream));
-      long bad = 0, total = 0, first = -1;
-      std::vector<unsigned long long> gbuf;
-      for (const auto& gr : h->sn_guards) {
-        gbuf.resize(gr.second);
-        HIP_TRY(hipMemcpy(gbuf.data(), h->sn_panel.p + gr.first, sizeof(double) * gr.second, hipMemcpyDeviceToHost));
-        for (long i = 0; i < gr.second; ++i)
-          if (gbuf[i] != ~0ULL) {
-            ++bad;
-            if (first < 0) first = gr.first + i;
-          }
-        total += gr.second;
-      }
-      std::fprintf(stderr, "[dpgo_hip] panel guard: %ld of %ld guard doubles in %zu gaps changed (first at %ld)\n", bad,
-                   total, h->sn_guards.size(), first);
-    }
-  }
-  auto c = make_ctx(h, flag, partials);
-  HIP_TRY(dpgo::launch_precond_finish(h->r, h->b, c, X, zraw, in, h->chol_state == 1 ? h->fac_not_pd.p : nullptr, rref,
-                                      h->chol_state == 1 ? 1 : 0, z_out, delta_out));
-  return DPGO_HIP_OK;
-}
+namespace {
 
 int sync_g(dpgo_hip_problem h) {
   if (!h->g_dirty) return DPGO_HIP_OK;
@@ -1443,8 +745,8 @@ int dpgo_hip_problem_create_batch(int num_agents, const int* poses_per_agent, in
   {
     const char* ev = std::getenv("DPGO_PANEL_CONTIG");
     const int cm = ev == nullptr ? 0 : std::atoi(ev);
-    if (cm & 1) h->sn_panel.alloc_flags = hipDeviceMallocContiguous;
-    if (cm & 2) h->sn_cpanel.alloc_flags = hipDeviceMallocContiguous;
+    if (cm & 1) h->ex.panel.alloc_flags = hipDeviceMallocContiguous;
+    if (cm & 2) h->ex.cpanel.alloc_flags = hipDeviceMallocContiguous;
   }
   const int T = h->num_tiles;
   if (h->tile_agent.ensure(T) || h->tile_start.ensure(T) || h->tile_count.ensure(T) ||
@@ -1731,27 +1033,6 @@ int dpgo_hip_set_tuning(int key, int value) {
   return DPGO_HIP_OK;
 }
 
-int dpgo_hip_exact_factor_info(dpgo_hip_problem h, long long* nodes, int* levels, int* max_s_tiles,
-                               long long* panel_doubles, double* factor_ms, int* factor_count) {
-  DPGO_TRY(check_handle(h));
-  if (!nodes || !levels || !max_s_tiles || !panel_doubles || !factor_ms || !factor_count)
-    return fail(DPGO_HIP_EINVAL, "null argument");
-  const long nn = h->sn_nodes;
-  *nodes = h->chol_doubles > 0 ? nn : 0;
-  *levels = static_cast<int>(h->sn_levels.size());
-  *max_s_tiles = 0;
-  if (*nodes > 0) {
-    std::vector<int> s(nn);
-    HIP_TRY(hipMemcpy(s.data(), h->sn_s.p, sizeof(int) * nn, hipMemcpyDeviceToHost));
-    for (int v : s) *max_s_tiles = std::max(*max_s_tiles, dpgo::sn_pad(v * h->b) / dpgo::kSnTile);
-  }
-  *panel_doubles = h->chol_doubles;
-  DPGO_TRY(resolve_factor_ms(h));
-  *factor_ms = h->chol_factor_ms;
-  *factor_count = h->chol_factor_count;
-  return DPGO_HIP_OK;
-}
-
 // Debug helper, not part of the ABI headers: the first 4 doubles of a fresh device allocation, so a test can confirm
 // that DPGO_POISON is in effect (NaN) before it trusts a poisoned run
 int dpgo_hip_debug_poison_probe(double* out4) {
@@ -1760,38 +1041,6 @@ int dpgo_hip_debug_poison_probe(double* out4) {
   dpgo::DevBuf<double> b;
   HIP_TRY(b.ensure(4));
   HIP_TRY(hipMemcpy(out4, b.p, sizeof(double) * 4, hipMemcpyDeviceToHost));
-  return DPGO_HIP_OK;
-}
-
-int dpgo_hip_exact_fallback_agents(dpgo_hip_problem h, int* flags, int* count) {
-  DPGO_TRY(check_handle(h));
-  if (!count) return fail(DPGO_HIP_EINVAL, "null argument");
-  std::vector<int> f(h->K, 0);
-  if (h->chol_state == 1 && h->fac_not_pd.p && h->fac_not_pd.n >= static_cast<size_t>(h->K)) {
-    HIP_TRY(hipMemcpyAsync(f.data(), h->fac_not_pd.p, sizeof(int) * h->K, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-  } else if (h->chol_state == 2) {
-    std::fill(f.begin(), f.end(), 1);
-  }
-  *count = 0;
-  for (int a = 0; a < h->K; ++a) *count += f[a] != 0;
-  if (flags) std::copy(f.begin(), f.end(), flags);
-  return DPGO_HIP_OK;
-}
-
-int dpgo_hip_exact_sweep_bytes(dpgo_hip_problem h, double* fwd_bytes, double* bwd_bytes) {
-  DPGO_TRY(check_handle(h));
-  if (!fwd_bytes || !bwd_bytes) return fail(DPGO_HIP_EINVAL, "null argument");
-  *fwd_bytes = h->chol_doubles > 0 ? h->sn_sweep_bytes_fwd : 0.0;
-  *bwd_bytes = h->chol_doubles > 0 ? h->sn_sweep_bytes_bwd : 0.0;
-  return DPGO_HIP_OK;
-}
-
-int dpgo_hip_exact_factor_flops(dpgo_hip_problem h, double* cholesky_flops, double* inverse_flops) {
-  DPGO_TRY(check_handle(h));
-  if (!cholesky_flops || !inverse_flops) return fail(DPGO_HIP_EINVAL, "null argument");
-  *cholesky_flops = h->chol_doubles > 0 ? h->chol_flops : 0.0;
-  *inverse_flops = h->chol_doubles > 0 ? h->chol_inv_flops : 0.0;
   return DPGO_HIP_OK;
 }
 
@@ -3311,7 +2560,7 @@ int dpgo_hip_set_edge_weights_dev(dpgo_hip_problem h, const double* w_dev) {
                                      h->slot_of_edge.p, w_dev, h->dinc_ptr.p, h->dinc.p, h->wslot.p, h->rec.p,
                                      h->diag.p, h->stream));
   HIP_TRY(dpgo::launch_bj_inverse_diag(h->b, static_cast<int>(h->N), qview(h), 0.1, h->minv.p, h->stream));
-  h->chol_state = 0;  // the exact factor follows Q
+  h->ex.state = 0;  // the exact factor follows Q
   h->host_weights_stale = true;
   h->w_dev_last = w_dev;
   return DPGO_HIP_OK;
@@ -3333,9 +2582,6 @@ double dpgo_hip_spmm_bytes_bsr(dpgo_hip_problem h) {
   return static_cast<double>(nnzb) * (b * b * 8.0 + 4.0) + static_cast<double>(h->N + 1) * 4.0 +
          2.0 * static_cast<double>(h->r) * b * static_cast<double>(h->N) * 8.0;
 }
-
-// launches of a standalone kernel benchmark that run before its timed window
-constexpr int kBenchWarmup = 3;
 
 int dpgo_hip_bench_hvp(dpgo_hip_problem h, const double* X_dev, double* V_dev, double* HV_dev, int reps, double* ms) {
   DPGO_TRY(ready(h));
@@ -3359,55 +2605,6 @@ int dpgo_hip_bench_hvp(dpgo_hip_problem h, const double* X_dev, double* V_dev, d
   float t = 0.f;
   HIP_TRY(hipEventElapsedTime(&t, e0, e1));
   *ms = static_cast<double>(t) / reps;
-  return DPGO_HIP_OK;
-}
-
-int dpgo_hip_bench_precond(dpgo_hip_problem h, const double* V_dev, int reps, double* ms_fwd, double* ms_bwd,
-                           double* panel_bytes) {
-  DPGO_TRY(ready(h));
-  DPGO_TRY(ensure_work(h));
-  if (reps <= 0 || !ms_fwd || !ms_bwd || !panel_bytes) return fail(DPGO_HIP_EINVAL, "bad argument");
-  DPGO_TRY(sync_chol(h));
-  *ms_fwd = *ms_bwd = 0.0;
-  *panel_bytes = 8.0 * static_cast<double>(h->chol_doubles);  // the stored tiles (dpgo_hip_exact_sweep_bytes: read)
-  if (h->chol_state != 1) return DPGO_HIP_OK;
-  dpgo::SnView v{h->sn_panel.p, h->sn_panel_off.p, h->sn_s.p,    h->sn_t.p,    h->sn_poses_off.p,
-                 h->sn_poses.p, h->sn_f_off.p,     h->sn_u_off.p, h->sn_cpos_off.p, h->sn_cpos.p,
-                 h->sn_contrib.p, h->sn_F.p,       h->sn_U.p,    h->sn_node_agent.p, h->state.p, dpgo::FLAG_NONE,
-                 h->fac_not_pd.p, h->sn_cpanel.p, h->sn_compact ? h->sn_cpanel_off.p : nullptr};
-  const int2* it = h->sn_items.p;
-  v.desc = sn_desc_on() ? h->sn_desc.p : nullptr;
-  v.items_base = it;
-  const int nl = static_cast<int>(h->sn_levels.size());
-  ScopedEvents sev(3);  // destroyed on every return, the early HIP_TRY ones included
-  HIP_TRY(sev.create());
-  hipEvent_t* ev = sev.ev.data();
-  double tf = 0.0, tb = 0.0;
-  for (int i = 0; i < kBenchWarmup + reps; ++i) {  // untimed applications first (see dpgo_hip_bench_hvp)
-    HIP_TRY(hipEventRecord(ev[0], h->stream));
-    for (int l = nl - 1; l >= 0; --l) {
-      const auto& L = h->sn_levels[l];
-      HIP_TRY(dpgo::launch_sn_assemble(h->r, h->b, v, it + L.asm0, L.asm_n, V_dev, h->stream));
-      HIP_TRY(dpgo::launch_sn_fwd_small(h->r, h->b, v, it + L.fws0, L.fws_n, h->tA.p, h->stream));
-      HIP_TRY(dpgo::launch_sn_fwd(h->r, h->b, v, it + L.fwd0, L.fwd_n, h->tA.p, h->stream));
-    }
-    HIP_TRY(hipEventRecord(ev[1], h->stream));
-    for (int l = 0; l < nl; ++l) {
-      const auto& L = h->sn_levels[l];
-      HIP_TRY(dpgo::launch_sn_bwd(h->r, h->b, v, it + L.bwd0, L.bwd_n, h->tA.p, h->tB.p, h->stream));
-    }
-    HIP_TRY(hipEventRecord(ev[2], h->stream));
-    HIP_TRY(hipEventSynchronize(ev[2]));
-    if (i >= kBenchWarmup) {
-      float a = 0.f, b = 0.f;
-      HIP_TRY(hipEventElapsedTime(&a, ev[0], ev[1]));
-      HIP_TRY(hipEventElapsedTime(&b, ev[1], ev[2]));
-      tf += a;
-      tb += b;
-    }
-  }
-  *ms_fwd = tf / reps;
-  *ms_bwd = tb / reps;
   return DPGO_HIP_OK;
 }
 

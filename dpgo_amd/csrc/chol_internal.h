@@ -41,6 +41,28 @@ inline long sn_tile_index(int ns_tiles, int I, int J) {
                       : static_cast<long>(ns_tiles) * (ns_tiles + 1) / 2 + static_cast<long>(I - ns_tiles) * ns_tiles + J;
 }
 
+// Plain constants and records the device side (kernels.h / kernels.hip) shares with the host schedule builder
+// (sn_schedule.cpp); no HIP type in any of them.
+constexpr int kSnSmallNs = 2;    // k_sn_fwd_small: nodes of at most this many S column tiles
+constexpr int kSnAsmRows = 256;  // frontal rows per assemble item, entries per assembly item: one workgroup's threads
+constexpr int kBK = 4;           // tiled factor: S tile columns per block of the right-looking loop (kind 5 per block)
+// leading dimension of a narrow supernode's compact panel (SnView::cpanel)
+constexpr int sn_compact_ld(int sb) { return (sb + 3) / 4 * 4; }
+// One sweep item (supernode, tile) with everything its workgroup needs before its first data load: one 64-byte
+// record instead of the item, then the node's agent, then the agent's flags, then the node's sizes and offsets --
+// three dependent round trips ahead of the panel loads, which on the deep levels (tens of thousands of workgroups
+// streaming 16-64 KB each) are most of a workgroup's life.
+struct alignas(64) SnItem {
+  int node, tile, agent, s, t, pad;
+  long f_off, u_off, panel_off, cpanel_off, poses_off;  // cpanel_off -1: tiles only
+};
+static_assert(sizeof(SnItem) == 64, "one cache line per sweep item");
+// One original entry of a supernode's S columns in the device factorisation's assembly (SnFactorView::ent)
+struct SnEntry {
+  int q, p;    // frontal pose positions (row q >= column p; p in S)
+  int s0, s1;  // edge sources src[s0 .. s1) (2 id + 1: block -M^T, 2 id: block -M); q == p: the diagonal block
+};
+
 struct SupernodalFactor {
   int n = 0, b = 0;
   std::vector<SnNode> nodes;  // postorder: every child before its parent; the root last

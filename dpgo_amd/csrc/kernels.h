@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "chol_internal.h"
 #include "dpgo_device.h"
 
 namespace dpgo {
@@ -222,16 +223,7 @@ struct GEdges {
 // [L_SS^-1 ; L_RS L_SS^-1] in kSnTileDev-square tiles), batch-global pose ids.  Frontal vectors F
 // ((S_pad + R_pad) scalar rows x r) and update vectors U (t b rows x r) are work space.
 constexpr int kSnTileDev = 64;
-constexpr int kSnSmallNs = 2;  // k_sn_fwd_small: nodes of at most this many S column tiles
-// One sweep item (supernode, tile) with everything its workgroup needs before its first data load: one 64-byte
-// record instead of the item, then the node's agent, then the agent's flags, then the node's sizes and offsets --
-// three dependent round trips ahead of the panel loads, which on the deep levels (tens of thousands of workgroups
-// streaming 16-64 KB each) are most of a workgroup's life.
-struct alignas(64) SnItem {
-  int node, tile, agent, s, t, pad;
-  long f_off, u_off, panel_off, cpanel_off, poses_off;  // cpanel_off -1: tiles only
-};
-static_assert(sizeof(SnItem) == 64, "one cache line per sweep item");
+static_assert(kSnAsmRows == kThreads, "assemble items: one row per thread of a workgroup");
 
 struct SnView {
   const double* panel;
@@ -261,8 +253,7 @@ struct SnView {
   // tiles (the same products in the same order, padding entries read as exact zeros); -1: tiles only.
   const double* cpanel = nullptr;
   const long* cpanel_off = nullptr;
-  // per item of items_base (SnItem): k_sn_fwd, k_sn_fwd_small and k_sn_bwd read their item's record there (null:
-  // from the arrays above)
+  // per item of items_base (SnItem): k_sn_fwd, k_sn_fwd_small and k_sn_bwd read their item's record there
   const SnItem* desc = nullptr;
   const int2* items_base = nullptr;
 };
@@ -271,7 +262,6 @@ struct SnView {
 // the compact matrix); launched after every factorisation
 hipError_t launch_sn_compact(int b, const double* panel, const long* panel_off, const int* s, const int* t,
                              const long* cpanel_off, double* cpanel, const int2* items, int count, hipStream_t stream);
-__host__ __device__ constexpr int sn_compact_ld(int sb) { return (sb + 3) / 4 * 4; }
 
 // Numeric supernodal factorisation of P = Q + shift I on the device (k_sn_factor), over the symbolic structure the
 // host built once (chol_internal.h supernodal_symbolic): one workgroup per supernode, one launch per tree level
@@ -281,10 +271,6 @@ __host__ __device__ constexpr int sn_compact_ld(int sb) { return (sb + 3) / 4 * 
 // current weights), then the children's update matrices (extend-add); then the blocked right-looking Cholesky
 // over the S tile columns (leaving L_SS, L_RS and the update matrix U = F_RR - L_RS L_RS^T in place) and the
 // panel [L_SS^-1 ; L_RS L_SS^-1] in the solve's tile layout.  Only the lower triangle of F is kept.
-struct SnEntry {
-  int q, p;    // frontal pose positions (row q >= column p; p in S)
-  int s0, s1;  // edge sources src[s0 .. s1) (2 id + 1: block -M^T, 2 id: block -M); q == p: the diagonal block
-};
 struct SnFactorView {
   const int* nodes;       // this launch's node ids (one level)
   const int* s;           // [nodes] poses in S

@@ -3683,24 +3683,9 @@ struct SnCompact {
   __amdgpu_buffer_rsrc_t r;
   int sb, tb, ld;
 };
-// The item's record: from SnView::desc (one load), or assembled from the per-node arrays
+// The item's record (SnView::desc): one load
 __device__ __forceinline__ SnItem sn_item(const SnView& v, const int2* items) {
-  const long idx = static_cast<long>(blockIdx.x);
-  if (v.desc != nullptr) return v.desc[(items - v.items_base) + idx];
-  const int2 it = items[idx];
-  SnItem d;
-  d.node = it.x;
-  d.tile = it.y;
-  d.agent = v.node_agent ? v.node_agent[it.x] : 0;
-  d.s = v.s[it.x];
-  d.t = v.t[it.x];
-  d.pad = 0;
-  d.f_off = v.f_off[it.x];
-  d.u_off = v.u_off[it.x];
-  d.panel_off = v.panel_off[it.x];
-  d.cpanel_off = v.cpanel_off ? v.cpanel_off[it.x] : -1;
-  d.poses_off = v.poses_off[it.x];
-  return d;
+  return v.desc[(items - v.items_base) + static_cast<long>(blockIdx.x)];
 }
 __device__ __forceinline__ bool sn_item_skipped(const SnView& v, const SnItem& d) {
   return v.node_agent && (agent_skipped(v.state, v.flag_kind, 0, d.agent) || (v.ident && v.ident[d.agent]));
@@ -4554,7 +4539,7 @@ __global__ __launch_bounds__(kThreads) void k_snf_asm(SnFactorView v, const int2
 }
 
 // kind 5 (the blocked trailing update): the tiles right of the current block of kSnfBlockK columns
-constexpr int kSnfBlockK = 4;
+constexpr int kSnfBlockK = kBK;
 // kind 5 with the next K's operands loaded during the current K's MFMAs (-DDPGO_SNF5_PIPE=0: load, then multiply)
 #ifndef DPGO_SNF5_PIPE
 #define DPGO_SNF5_PIPE 1

@@ -9,10 +9,12 @@
 
 #include "../../include/dpgo_hip.h"
 #include "kernels.h"
+#include "sn_schedule.h"
 
 namespace dpgo {
 
 int fail(int code, const std::string& msg);
+inline int check_handle(dpgo_hip_problem h) { return h ? DPGO_HIP_OK : fail(DPGO_HIP_EINVAL, "null problem handle"); }
 int usable_devices();
 
 // Debug runs (DPGO_POISON=1): every fresh device allocation, and the exact preconditioner's frontal / panel /
@@ -79,6 +81,56 @@ struct DevBuf {
   }
 };
 
+// The exact preconditioner's device state (exact.cpp): supernodal Cholesky of Q + 0.1 I (chol.cpp), one launch per
+// tree level and sweep.  The tables are SnSchedule's (sn_schedule.h), uploaded under the same names.
+struct ExactPrecond {
+  int state = 0;  // 0 stale, 1 ready, 2 Q + 0.1 I not positive definite (identity, as the reference)
+  long nodes = 0;          // supernodes of the current symbolic structure (s may be larger: capacity)
+  long panel_doubles = 0;  // doubles of the stored tiles (guard gaps included)
+  DevBuf<double> panel, F, U;
+  DevBuf<long> panel_off, f_off, u_off;
+  DevBuf<int> s, t, poses_off, poses, cpos_off, cpos;
+  DevBuf<int2> contrib, items;
+  DevBuf<int> node_agent;       // [nodes] batch agent of each supernode (per-agent skip in the sweeps)
+  std::vector<SnLevel> levels;  // index = depth (0 = the roots)
+  // narrow supernodes' compact panels (SnView::cpanel): per node its offset (-1: tiles only), the copy's items
+  // (node, 64-row block) for launch_sn_compact after every factorisation, and the bytes a sweep then reads
+  DevBuf<double> cpanel;
+  DevBuf<long> cpanel_off;
+  DevBuf<int2> citems;
+  DevBuf<SnItem> desc;  // [items] per sweep item its node's record (SnView::desc)
+  int citems_n = 0;
+  bool compact = false;
+  double sweep_bytes_fwd = 0.0, sweep_bytes_bwd = 0.0;
+  // DPGO_PANEL_GUARD (debug runs): (offset, doubles) of the NaN gap after every supernode's panel and after the last
+  std::vector<std::pair<long, long>> guards;
+  double flops = 0.0;      // the factorisation's classic flop count: sum over supernodes s^3/3 + s^2 t + s t^2
+  double inv_flops = 0.0;  // the panels' extra: L_SS^-1 (s^3/3) and L_RS L_SS^-1 (s^2 t) per supernode
+  // device numeric factorisation (TUNE_DEVICE_CHOL, edge-stream Q): the symbolic structure is built once per Q
+  // pattern (sym_ready); every refresh after a reweighting re-runs only k_sn_factor, level by level
+  bool sym_ready = false;
+  std::vector<int> level_off;  // [depth + 1] into fac_nodes
+  DevBuf<int> fac_nodes, ch_off, ch, tp_off, tp, ent_off, src;
+  // [K] per agent: 1 = its factorisation met a non-positive pivot (identity preconditioner for that agent only,
+  // src/QuadraticProblem.cpp:81-86); written by the device factor, or uploaded by the host factorisation
+  DevBuf<int> not_pd;
+  DevBuf<long> fac_off;
+  DevBuf<SnEntry> ent;
+  DevBuf<double> fac_F[2];  // frontal matrices of the even / odd tree depths
+  // tree levels factorised tile-parallel (few, large supernodes): per depth the launch sequence of
+  // launch_sn_factor_tiled over titems (empty: one workgroup per node, k_sn_factor)
+  std::vector<std::vector<FacLaunch>> fac_seq;
+  DevBuf<int2> titems;
+  double factor_ms = 0.0;       // the last device factorisation (hipEvent), for the benches
+  bool factor_pending = false;  // fac_ev holds a factorisation whose time is not yet in factor_ms
+  int factor_count = 0;
+  hipEvent_t fac_ev[2] = {nullptr, nullptr};  // the device factorisation's timing (created once per handle)
+  ~ExactPrecond() {
+    for (auto e : fac_ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+
 }  // namespace dpgo
 
 struct dpgo_hip_problem_s {
@@ -129,61 +181,15 @@ struct dpgo_hip_problem_s {
 
   int precon = DPGO_PRECON_BLOCK_JACOBI;
 
-  // exact preconditioner: supernodal Cholesky of Q + 0.1 I (chol.cpp), one launch per tree level and sweep
-  int chol_state = 0;  // 0 stale, 1 ready, 2 Q + 0.1 I not positive definite (identity, as the reference)
-  dpgo::DevBuf<double> sn_panel, sn_F, sn_U;
-  dpgo::DevBuf<long> sn_panel_off, sn_f_off, sn_u_off;
-  dpgo::DevBuf<int> sn_s, sn_t, sn_poses_off, sn_poses, sn_cpos_off, sn_cpos;
-  dpgo::DevBuf<int2> sn_contrib, sn_items;
-  dpgo::DevBuf<int> sn_node_agent;  // [nodes] batch agent of each supernode (per-agent skip in the sweeps)
-  struct SnLevel {  // item ranges into sn_items of one tree depth
-    int asm0 = 0, asm_n = 0, fws0 = 0, fws_n = 0, fwd0 = 0, fwd_n = 0, bwd0 = 0, bwd_n = 0;  // fws: k_sn_fwd_small's
-  };
-  std::vector<SnLevel> sn_levels;  // index = depth (0 = the roots)
-  // narrow supernodes' compact panels (SnView::cpanel): per node its offset (-1: tiles only), the copy's items
-  // (node, 64-row block) for launch_sn_compact after every factorisation, and the bytes a sweep then reads
-  dpgo::DevBuf<double> sn_cpanel;
-  dpgo::DevBuf<long> sn_cpanel_off;
-  dpgo::DevBuf<int2> sn_citems;
-  dpgo::DevBuf<dpgo::SnItem> sn_desc;  // [items] per sweep item its node's record (SnView::desc)
-  int sn_citems_n = 0;
-  bool sn_compact = false;
-  double sn_sweep_bytes_fwd = 0.0, sn_sweep_bytes_bwd = 0.0;
-  long chol_doubles = 0;
+  dpgo::ExactPrecond ex;  // exact preconditioner: supernodal Cholesky of Q + 0.1 I
   dpgo::DevBuf<int4> tile_meta;
   // edge-stream records and diagonal blocks at unit weights (kept by the engine under a robust cost): the central
   // evaluation of examples/MultiRobotExample.cpp:229-235 reads the dataset's Q, not the reweighted one
   dpgo::DevBuf<double> rec_unit, diag_unit;
   bool central_unit = false;  // qview() serves rec_unit / diag_unit  // edge-stream Q: per tile stage ranges (LaunchCtx::tile_meta); empty otherwise
-  long sn_nodes = 0;             // supernodes of the current symbolic structure (sn_s may be larger: capacity)
-  // DPGO_PANEL_GUARD (debug runs): (offset, doubles) of the NaN gap after every supernode's panel and after the last
-  std::vector<std::pair<long, long>> sn_guards;
-  double chol_flops = 0.0;       // the factorisation's classic flop count: sum over supernodes s^3/3 + s^2 t + s t^2
-  double chol_inv_flops = 0.0;   // the panels' extra: L_SS^-1 (s^3/3) and L_RS L_SS^-1 (s^2 t) per supernode
-  // device numeric factorisation (TUNE_DEVICE_CHOL, edge-stream Q): the symbolic structure is built once per Q
-  // pattern (sn_sym_ready); every refresh after a reweighting re-runs only k_sn_factor, level by level
-  bool sn_sym_ready = false;
-  std::vector<int> fac_level_off;  // [depth + 1] into fac_nodes
-  dpgo::DevBuf<int> fac_nodes, fac_ch_off, fac_ch, fac_tp_off, fac_tp, fac_ent_off, fac_src;
-  // [K] per agent: 1 = its factorisation met a non-positive pivot (identity preconditioner for that agent only,
-  // src/QuadraticProblem.cpp:81-86); written by the device factor, or uploaded by the host factorisation
-  dpgo::DevBuf<int> fac_not_pd;
-  dpgo::DevBuf<long> fac_off;
-  dpgo::DevBuf<dpgo::SnEntry> fac_ent;
-  dpgo::DevBuf<double> fac_F[2];  // frontal matrices of the even / odd tree depths
-  // tree levels factorised tile-parallel (few, large supernodes): per depth the launch sequence of
-  // launch_sn_factor_tiled over fac_titems (empty: one workgroup per node, k_sn_factor)
-  struct FacLaunch {
-    int kind, param, off, count;
-  };
-  std::vector<std::vector<FacLaunch>> fac_seq;
-  dpgo::DevBuf<int2> fac_titems;
-  double chol_factor_ms = 0.0;    // the last device factorisation (hipEvent), for the benches
-  bool chol_factor_pending = false;  // fac_ev holds a factorisation whose time is not yet in chol_factor_ms
-  int chol_factor_count = 0;
   // host copy of the edge-stream incidences (sync_q_edges), for the factor's assembly tables
   std::vector<int> h_inc_ptr;
-  std::vector<int2> h_inc;
+  std::vector<dpgo::SnPair> h_inc;
 
   // work
   dpgo::DevBuf<double> x1, x2, g, g2, S, S2, eta, rv, z, delta, Hdelta, tA, tB;
@@ -234,10 +240,7 @@ struct dpgo_hip_problem_s {
   double timed_ms[dpgo::kSpmmModes] = {};
   long long timed_n[dpgo::kSpmmModes] = {};
   double timed_frac[dpgo::kSpmmModes] = {};  // summed TimedLaunch::frac: full-batch launch equivalents
-  hipEvent_t fac_ev[2] = {nullptr, nullptr};  // the device factorisation's timing (created once per handle)
   ~dpgo_hip_problem_s() {
-    for (auto e : fac_ev)
-      if (e) (void)hipEventDestroy(e);
     for (auto& t : timed) {
       (void)hipEventDestroy(t.a);
       (void)hipEventDestroy(t.b);
@@ -284,4 +287,33 @@ int spmm_launch(dpgo_hip_problem h, int mode, const LaunchCtx& c, const SpmmArgs
 int take_spmm_times(dpgo_hip_problem h, double* ms_per_mode, long long* launches_per_mode, double* batch_equiv);
 // fold completed (wait: all) timed launches into the handle's per-mode running totals
 int drain_timed(dpgo_hip_problem h, bool wait);
+// one agent's Q as block-sparse rows, whichever format it was set in
+void agent_bsr(dpgo_hip_problem h, int a, HostBSR& out);
+
+// Events created for one scope and destroyed on every exit from it (an early HIP_TRY return included)
+struct ScopedEvents {
+  std::vector<hipEvent_t> ev;
+  explicit ScopedEvents(size_t n) : ev(n, nullptr) {}
+  ~ScopedEvents() {
+    for (auto e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+  hipError_t create() {
+    for (auto& e : ev)
+      if (!e) {
+        const hipError_t r = hipEventCreate(&e);
+        if (r != hipSuccess) return r;
+      }
+    return hipSuccess;
+  }
+};
+// launches of a standalone kernel benchmark that run before its timed window
+constexpr int kBenchWarmup = 3;
+
+// exact.cpp: the exact preconditioner.  sync_chol brings the factor up to date with Q (symbolic build + upload on a
+// new pattern, the numeric factorisation alone after a reweighting); exact_precond applies it:
+// z = P_X(in (Q + 0.1 I)^-1) per agent, then projection + partials <z, rref>, |rref|^2 (pass rref = in).
+int sync_chol(dpgo_hip_problem h);
+int exact_precond(dpgo_hip_problem h, const double* in, double* z_out, double* delta_out, const double* X,
+                  const double* rref, double* partials, int flag);
 }  // namespace dpgo

@@ -162,6 +162,27 @@ def test_cpp_host_cases():
         assert f"[PASS] {name}" in out, out[-3000:]
 
 
+def test_cpp_sn_schedule(tmp_path):
+    """The exact preconditioner's host schedule builder (dpgo_amd/csrc/sn_schedule.cpp) against the supernodal trees
+    and incidence lists, every option combination the GPU tests use: node layout, sweep items per level, item
+    records, compact panels, extend-add lists, the factor's assembly entries and the tiled launch sequence.  The
+    program builds its grids itself; the two dataset patterns (block size, poses, edge endpoints) are handed over as
+    text."""
+    binary = os.path.join(ROOT, "dpgo_amd", "cpp", "build", "test_sn_schedule")
+    assert os.path.exists(binary), "C++ tests not built (run __graft_entry__.build())"
+    names = ["smallGrid3D", "input_INTEL_g2o"]
+    for name in names:
+        meas = load_meas(name)
+        with open(tmp_path / f"{name}.pat", "w") as f:
+            f.write(f"{meas.d + 1} {meas.num_poses} {len(meas.p1)}\n")
+            f.writelines(f"{int(i)} {int(j)}\n" for i, j in zip(meas.p1, meas.p2))
+    p = subprocess.run([binary, str(tmp_path)], capture_output=True, text=True, timeout=300)
+    out = p.stdout + p.stderr
+    assert p.returncode == 0, out[-3000:]
+    for name in ["Grid4OneAgent", "Grid6EightAgents", "Grid12OneAgent", "LonePoseAgent"] + names:
+        assert f"[PASS] {name}" in out, out[-3000:]
+
+
 @pytest.mark.parametrize("name,agents", [("smallGrid3D", 5), ("input_INTEL_g2o", 4), ("city10000", 8)])
 def test_distributed_initialization_matches_oracle(H, name, agents):
     """PGOAgent::localInitialization per agent + initializeInGlobalFrame (host Cholesky path) vs the
