@@ -134,8 +134,7 @@ int dpgo::spmm_launch(dpgo_hip_problem h, int mode, const LaunchCtx& c, const Sp
     HIP_TRY(dpgo::launch_spmm(h->r, h->b, mode, c, qview(h), a));
     return DPGO_HIP_OK;
   }
-  dpgo_hip_problem_s::TimedLaunch t{mode, nullptr, nullptr,
-                                    static_cast<double>(c.num_tiles) / std::max(h->num_tiles, 1)};
+  dpgo_hip_problem_s::TimedLaunch t{mode, nullptr, nullptr, c.num_tiles};
   HIP_TRY(pooled_event(h, &t.a));
   HIP_TRY(pooled_event(h, &t.b));
   HIP_TRY(hipEventRecord(t.a, c.stream));
@@ -167,7 +166,7 @@ int dpgo::drain_timed(dpgo_hip_problem h, bool wait) {
     if (t.mode >= 0 && t.mode < dpgo::kSpmmModes) {
       h->timed_ms[t.mode] += v;
       h->timed_n[t.mode] += 1;
-      h->timed_frac[t.mode] += t.frac;
+      h->timed_tiles[t.mode] += t.tiles;
     }
     h->ev_pool.push_back(t.a);
     h->ev_pool.push_back(t.b);
@@ -181,10 +180,10 @@ int dpgo::take_spmm_times(dpgo_hip_problem h, double* ms, long long* launches, d
   for (int m = 0; m < dpgo::kSpmmModes; ++m) {
     ms[m] += h->timed_ms[m];
     launches[m] += h->timed_n[m];
-    batch_equiv[m] += h->timed_frac[m];
+    batch_equiv[m] += static_cast<double>(h->timed_tiles[m]) / std::max(h->num_tiles, 1);
     h->timed_ms[m] = 0.0;
     h->timed_n[m] = 0;
-    h->timed_frac[m] = 0.0;
+    h->timed_tiles[m] = 0;
   }
   return DPGO_HIP_OK;
 }
@@ -1463,14 +1462,55 @@ int dpgo::optimize_dev_status(dpgo_hip_problem h, const dpgo_opt_params* params,
     // near-empty launches).  Adaptive (default): when the previous call's tCG took CG steps.
     const int la = h->tuning[dpgo::TUNE_TCG_LOOKAHEAD];
     const bool all_ahead = merged && single && full0 && la != 1 && (la == 2 || !h->predict_boundary);
-    const bool split = all_ahead && dpgo::merged_split(h);
+    // TUNE_TCG_BLOCK: the batch's agents in blocks of consecutive agents, each block's iterations queued depth-first
+    // (agent boundaries in tcg_blocks; fewer than two blocks: not applied)
+    std::vector<int> tcg_blocks;
+    if (all_ahead) dpgo::merged_blocks(h, &tcg_blocks);
+    const bool blocked = tcg_blocks.size() > 2;
+    if (round == 0) h->tcg_blocks_last = 0;  // (a call's Runs: the first and its radius-shrink retries)
+    if (blocked) h->tcg_blocks_last = static_cast<int>(tcg_blocks.size()) - 1;
+    const bool split = all_ahead && !blocked && dpgo::merged_split(h);
     // The classic sequence (the exact preconditioner) queued the same way on request (TUNE_TCG_LOOKAHEAD = 2 only):
     // every iteration at once, agents that stopped skip their tiles and their supernodes, no status round trip
     // inside tCG.  Bitwise the one-ahead sequence (test_exact_lookahead_bitwise) but not the default: the dead
     // iterations cost more than the round trips they save (same-process A/B: C4 17.4 vs 16.7 ms/step, C5 101.8 vs
     // 100.8, profiles/r03ze_*).
     const bool classic_ahead = !merged && single && !qf0 && P.tr_max_inner > 0 && la == 2;
-    if (split) {
+    if (blocked) {
+      // Block b runs its tr_max_inner iterations back to back on stream b % S (0: the launch stream, s:
+      // split_stream[s - 1]), so two touches of a block's lines are one block launch apart instead of one batch
+      // launch and at most S blocks are in flight.  Queued wave by wave (S blocks), a wave's blocks interleaved per
+      // iteration so every stream has work from the first launches on.  One pair of tile orders per wave and
+      // iteration: each block's consecutive launches alternate direction.
+      const int B = static_cast<int>(tcg_blocks.size()) - 1;
+      const int S = std::max(1, std::min({h->tuning[dpgo::TUNE_TCG_BLOCK_STREAMS], 4, B}));
+      static_assert(dpgo_hip_problem_s::kMaxSplit >= 4, "streams of TUNE_TCG_BLOCK_STREAMS");
+      if (S > 1 && !h->split_fork) HIP_TRY(hipEventCreateWithFlags(&h->split_fork, hipEventDisableTiming));
+      for (int s = 0; s + 1 < S; ++s) {
+        if (!h->split_stream[s]) HIP_TRY(hipStreamCreateWithFlags(&h->split_stream[s], hipStreamNonBlocking));
+        if (!h->split_join[s]) HIP_TRY(hipEventCreateWithFlags(&h->split_join[s], hipEventDisableTiming));
+      }
+      auto on = [&](int s) { return s == 0 ? h->stream : h->split_stream[s - 1]; };
+      if (S > 1) {
+        HIP_TRY(hipEventRecord(h->split_fork, h->stream));
+        for (int s = 1; s < S; ++s) HIP_TRY(hipStreamWaitEvent(on(s), h->split_fork, 0));
+      }
+      for (int w = 0; w < B; w += S) {
+        for (int j = 0; j < P.tr_max_inner; ++j) {
+          const int mode = j == 0 ? dpgo::MODE_HESS_QF_M : dpgo::MODE_HESS_M;
+          const int oh = dpgo::tile_order_next(h);
+          const int ou = tail_fuse && j + 1 == P.tr_max_inner ? 0 : dpgo::tile_order_next(h);
+          for (int s = 0; s < S && w + s < B; ++s)
+            DPGO_TRY(launch_merged_range(j, mode, dpgo::FLAG_TCG, dpgo::OP_TCG_STEP_CHECK, tcg_blocks[w + s],
+                                         tcg_blocks[w + s + 1], on(s), oh, ou));
+        }
+      }
+      for (int s = 1; s < S; ++s) {
+        HIP_TRY(hipEventRecord(h->split_join[s - 1], on(s)));
+        HIP_TRY(hipStreamWaitEvent(h->stream, h->split_join[s - 1], 0));
+      }
+      cg_agents = true;
+    } else if (split) {
       // groups of agents [a_g, a_g+1): two halves (values 1, 2), four groups (3) or one group per agent up to
       // eight (4); group 0 on the launch stream, group g on split_stream[g - 1]
       const int sv = h->tuning[dpgo::TUNE_SPLIT_STREAMS];
@@ -1666,6 +1706,32 @@ bool dpgo::merged_split(dpgo_hip_problem h) {
   constexpr int kSplitMaxTiles = 4096;
   return h->K >= 2 && h->num_tiles <= kSplitMaxTiles && h->fuse_finalize == 0 &&
          h->tuning[dpgo::TUNE_SPLIT_STREAMS] > 0;
+}
+
+// TUNE_TCG_BLOCK: the agent boundaries of the blocks the merged tCG loop is queued in, blocks[0] = 0 < ... <
+// blocks.back() = K.  Runs of consecutive agents formed greedily: an agent joins the current block while the block
+// stays within the target tile count, and a block has at least one agent (an agent larger than the target is a block
+// of its own).  Left with fewer than two blocks -- the unblocked queueing -- when the key is off, the finalize is fused
+// into the SpMM, or the whole batch fits in one block.
+void dpgo::merged_blocks(dpgo_hip_problem h, std::vector<int>* blocks) {
+  blocks->clear();
+  const int target = h->tuning[dpgo::TUNE_TCG_BLOCK];
+  if (target <= 0 || h->K < 2 || h->fuse_finalize != 0 || h->num_tiles <= target) return;
+  blocks->push_back(0);
+  int t_block = h->h_agent_tile_off[0];  // first tile of the current block
+  for (int a = 1; a < h->K; ++a)
+    if (h->h_agent_tile_off[a + 1] - t_block > target) {
+      blocks->push_back(a);
+      t_block = h->h_agent_tile_off[a];
+    }
+  blocks->push_back(h->K);
+}
+
+int dpgo_hip_tcg_blocks(dpgo_hip_problem h, int* blocks_last, int* agent_tiles) {
+  DPGO_TRY(check_handle(h));
+  if (blocks_last) *blocks_last = h->tcg_blocks_last;
+  for (int a = 0; agent_tiles && a < h->K; ++a) agent_tiles[a] = h->h_agent_tile_off[a + 1] - h->h_agent_tile_off[a];
+  return DPGO_HIP_OK;
 }
 
 int dpgo::eval_sums_dev(dpgo_hip_problem h, const double* X) {

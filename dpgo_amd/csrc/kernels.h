@@ -358,7 +358,13 @@ enum TuneKey { TUNE_SPMM_VARIANT = 0, TUNE_EDGE_VARIANT = 1, TUNE_EPI_PREFETCH =
                TUNE_NEXT_Y = 15,  // engine: 1 the non-selected pass over the colour selected next also writes that
                                   // colour's next updateY and status XPrev (PolarNext), and the selected colour's
                                   // own pass is skipped when the prediction held; 0 both passes
-               TUNE_COUNT = 16 };
+               TUNE_TCG_BLOCK = 16,  // merged tCG queued at once: target tiles per block of consecutive agents; a
+                                     // block runs all its iterations before the stream's next block starts
+                                     // (DESIGN.md 3.11); 0 off, and off for a batch of at most this many tiles.
+                                     // Default 2000 (8 agents of the 1M colour) on two streams: -4.8 % ms/step
+                                     // at 1M; on one stream every block size is slower than off
+               TUNE_TCG_BLOCK_STREAMS = 17,  // blocks in flight (block b on stream b % S), 1..4 (default 2)
+               TUNE_COUNT = 18 };
 // dd_mask of the merged tCG partials for the kernel a handle with these tuning keys and Q format runs
 inline int merged_dd_mask(int fmt, const int* tuning) {
   return fmt == QFMT_EDGES && tuning[TUNE_SPMM_V2] > 0 ? kMergedDdSlots : kMergedDdSlotsV1;

@@ -203,6 +203,9 @@ struct dpgo_hip_problem_s {
   static constexpr int kMaxSplit = 8;
   hipStream_t split_stream[kMaxSplit - 1] = {};
   hipEvent_t split_fork = nullptr, split_join[kMaxSplit - 1] = {};
+  // TUNE_TCG_BLOCK: agent blocks the last optimise call queued its merged tCG loop in (0: the unblocked queueing);
+  // the blocks' streams and events are the split's
+  int tcg_blocks_last = 0;
   dpgo::DevBuf<dpgo::AgentState> state;
   std::vector<dpgo::AgentState> h_state;
   // per-agent arrival counts of a k_spmm with a fused finalize (0 between launches)
@@ -232,14 +235,16 @@ struct dpgo_hip_problem_s {
   struct TimedLaunch {
     int mode;
     hipEvent_t a, b;
-    double frac;  // the launch's tiles / the batch's tiles (a half-batch launch of the split merged tCG: ~0.5)
+    int tiles;  // the launch's tiles (a launch over part of the batch: an agent group or block of the merged tCG)
   };
   std::vector<TimedLaunch> timed;
   std::vector<hipEvent_t> ev_pool;
   // completed timed launches drained out of `timed` (bounded event count on long timed runs)
   double timed_ms[dpgo::kSpmmModes] = {};
   long long timed_n[dpgo::kSpmmModes] = {};
-  double timed_frac[dpgo::kSpmmModes] = {};  // summed TimedLaunch::frac: full-batch launch equivalents
+  // summed TimedLaunch::tiles: over the batch's tile count the full-batch launch equivalents, exact when the timed
+  // sub-launches add up to whole batches
+  long long timed_tiles[dpgo::kSpmmModes] = {};
   ~dpgo_hip_problem_s() {
     for (auto& t : timed) {
       (void)hipEventDestroy(t.a);
@@ -275,6 +280,7 @@ int optimize_dev_status(dpgo_hip_problem h, const dpgo_opt_params* params, const
                         const int* agent_enabled_host, dpgo_opt_result* results, const StatusArgs* st);
 // f / |grad|^2 / <G, X> per agent at X into the handle's sums (OP_SUM, nq 3): asynchronous
 bool merged_split(dpgo_hip_problem h);  // TUNE_SPLIT_STREAMS applies to this batch (capi.cpp)
+void merged_blocks(dpgo_hip_problem h, std::vector<int>* blocks);  // TUNE_TCG_BLOCK's agent blocks (capi.cpp)
 int eval_sums_dev(dpgo_hip_problem h, const double* X);
 // the same with the edge-stream Q at unit weights (keep_unit_q: the copy taken before any reweighting)
 int eval_sums_unit_dev(dpgo_hip_problem h, const double* X);

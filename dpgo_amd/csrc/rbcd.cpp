@@ -1487,6 +1487,15 @@ int dpgo_rbcd_next_y_counters(dpgo_rbcd e, long long* skipped, long long* mispre
   return DPGO_HIP_OK;
 }
 
+int dpgo_rbcd_tcg_blocks(dpgo_rbcd e, int color, int* blocks_last, int* agent_tiles) {
+  if (!e || color < 0 || color >= e->ncolors) return fail(DPGO_HIP_EINVAL, "bad colour");
+  if (!e->prob[color]) {
+    if (blocks_last) *blocks_last = 0;
+    return DPGO_HIP_OK;
+  }
+  return dpgo_hip_tcg_blocks(e->prob[color], blocks_last, agent_tiles);
+}
+
 int dpgo_rbcd_counters(dpgo_rbcd e, long long* agent_updates, long long* iterations) {
   if (!e) return fail(DPGO_HIP_EINVAL, "null engine");
   if (agent_updates) *agent_updates = e->agent_updates;

@@ -725,6 +725,7 @@ _SIGS2 = [
     ("dpgo_rbcd_bench_spmm", [C.c_void_p, C.c_int, C.c_int, _dp, _dp], C.c_int),
     ("dpgo_rbcd_counters", [C.c_void_p, _lp, _lp], C.c_int),
     ("dpgo_rbcd_next_y_counters", [C.c_void_p, _lp, _lp], C.c_int),
+    ("dpgo_rbcd_tcg_blocks", [C.c_void_p, C.c_int, _ip, _ip], C.c_int),
     ("dpgo_rbcd_spmm_bytes", [C.c_void_p, C.c_int, _dp, _dp], C.c_int),
     ("dpgo_rbcd_bench_hvp", [C.c_void_p, C.c_int, C.c_int, _dp], C.c_int),
     ("dpgo_rbcd_reset_stream", [C.c_void_p], C.c_int),
@@ -1358,3 +1359,11 @@ class Rbcd:
         s, m = C.c_longlong(), C.c_longlong()
         _check(lib().dpgo_rbcd_next_y_counters(self.h, C.byref(s), C.byref(m)))
         return s.value, m.value
+
+    def tcg_blocks(self, color):
+        """(blocks, agent_tiles): the agent blocks the colour's last update queued its merged tCG loop in (tuning key
+        16; 0: the unblocked queueing ran) and the tile count of each of the colour's agents, in batch order."""
+        n = C.c_int()
+        tiles = np.zeros(max(int(self.agents_per_color[color]), 1), np.int32)
+        _check(lib().dpgo_rbcd_tcg_blocks(self.h, int(color), C.byref(n), tiles.ctypes.data_as(_ip)))
+        return n.value, tiles[:int(self.agents_per_color[color])]

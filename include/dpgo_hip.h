@@ -340,6 +340,9 @@ int dpgo_hip_escape(dpgo_hip_problem h_next, const double* X, const double* v, d
  * ahead, 2 all at once; the classic sequence of the exact preconditioner queues all at once only with 2).  key 8: 1 = second-visit record staging (set before Q).  key 9: 1 = the agent
  * status by its own pass instead of folded into the rho test.  key 10: merged tCG iterations of a small
  * batch (<= 4,096 tiles) in two agent halves on two streams (1, default; 0 off; 2 the halves out of phase).
+ * key 16: merged tCG iterations queued at once in blocks of consecutive agents of at most this many tiles, each block's
+ * iterations back to back (default 2000; 0 off; a batch of at most this many tiles is queued as without the key).
+ * key 17: blocks in flight, 1..4 (block b on stream b % value; default 2).
  * DESIGN.md records each key's measurement.  These are the process DEFAULTS: a handle copies them when it is
  * created, so handles created afterwards follow; dpgo_hip_problem_set_tuning changes one existing handle. */
 int dpgo_hip_set_tuning(int key, int value);
@@ -372,6 +375,10 @@ int dpgo_hip_exact_sweep_bytes(dpgo_hip_problem h, double* fwd_bytes, double* bw
 int dpgo_hip_get_tuning(int key, int* value);
 /* The same keys on one existing handle (A/B timing of variants on one problem without rebuilding it). */
 int dpgo_hip_problem_set_tuning(dpgo_hip_problem h, int key, int value);
+/* Tuning key 16: the number of agent blocks the handle's last optimise call queued its merged tCG loop in (0: the
+ * unblocked queueing ran), and the tile count of every agent of the batch (agent_tiles[num_agents]); either may be
+ * null. */
+int dpgo_hip_tcg_blocks(dpgo_hip_problem h, int* blocks_last, int* agent_tiles);
 /* Algorithmic HBM bytes of one X.Q SpMM over this handle: BSR blocks + indices + X + Y, or, for
  * an edge-stream Q, every edge record once + 8 B per incidence + pointers + X + Y. */
 double dpgo_hip_spmm_bytes(dpgo_hip_problem h);

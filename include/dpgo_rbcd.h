@@ -281,6 +281,10 @@ int dpgo_rbcd_counters(dpgo_rbcd e, long long* agent_updates, long long* iterati
    non-selected pass had already written that colour's Y / XPrev, and write-ahead records that did not match the
    next call (another colour, a restart or reweighting, another alpha) and were dropped.  Either may be null. */
 int dpgo_rbcd_next_y_counters(dpgo_rbcd e, long long* skipped, long long* mispredicted);
+/* Tuning key 16 (blocked tCG queueing) on colour class c: dpgo_hip_tcg_blocks of the colour's batch -- the blocks its
+   last update was queued in (0: unblocked) and the tile count of each of its agents on this rank, in batch order
+   (agent_tiles[agents of the colour on this rank]).  Either may be null. */
+int dpgo_rbcd_tcg_blocks(dpgo_rbcd e, int color, int* blocks_last, int* agent_tiles);
 
 /* Central evaluation (examples/MultiRobotExample.cpp:229-235): this rank's share of the whole-graph
  * cost f(X) = 1/2 <X Q, X> (sum over ranks = the central cost; Q is the dataset's, unit weights, as the

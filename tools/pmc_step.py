@@ -5,7 +5,10 @@ CG regime (burn-in as the default bench), each with a device copy of known size 
 (FETCH_SIZE on gfx950 under-counts wide reads; factor = copy read bytes / FETCH_SIZE(copy), same pass).
 
 Per SpMM mode the median over the mode's last launches (all in the CG regime, every agent active) is
-reported; bench.py folds profiles/*_pmc_traffic.json "kernels" into its roofline "traffic".
+reported; bench.py folds profiles/*_pmc_traffic.json "kernels" into its roofline "traffic".  With the merged tCG loop
+queued in agent blocks (tuning key 16) a mode's launches cover part of a colour each: "per launch" then means per
+full-batch equivalent, the sum over the sub-launches that make up one colour (see per_kernel), which is what bench.py
+divides by its per-batch-equivalent event time.
 
 Usage on the GPU box:  python tools/pmc_step.py run <outdir>
                        python tools/pmc_step.py summarize <outdir> > profiles/rNN_pmc_traffic.json
@@ -43,17 +46,51 @@ def _db(outdir, ctr):
     return found[0]
 
 
+def _workgroups_expr(c):
+    """SQL for a dispatch's workgroup count in counters_collection (None when the view has no grid columns)."""
+    cols = {r[1] for r in c.execute("pragma table_info(counters_collection)")}
+    for g, w in (("grid_size", "workgroup_size"), ("grid_size_x", "workgroup_size_x"), ("grid_x", "workgroup_x")):
+        if g in cols and w in cols:
+            return f"{g} / max({w}, 1)"
+    return None
+
+
 def per_kernel(db, ctr, last=200):
-    """{kernel name: median of the last `last` launches' counter value}, in dispatch order."""
+    """{kernel name: (counter value per full-batch launch equivalent over the kernel's last `last` equivalents, launches,
+    largest single value, sub-launches per equivalent)}, in dispatch order.
+
+    A pose-tiled launch has one workgroup per tile, and the largest k_spmm launch of the run covers a whole colour
+    (EVAL_TCG always does).  A kernel whose last launches all cover the batch reports their median, as before the
+    merged tCG loop was queued in agent blocks (TUNE_TCG_BLOCK); one launched over part of the batch reports the sum
+    over the sub-launches that make up one batch: summed values / (summed workgroups / the batch's workgroups)."""
     c = sqlite3.connect(db)
+    wg = _workgroups_expr(c)
     acc = {}
-    for name, val in c.execute("select kernel_name, value from counters_collection where counter_name=? "
-                               "order by dispatch_id", (ctr,)):
-        acc.setdefault(name, []).append(val)
+    for name, val, n in c.execute(f"select kernel_name, value, {wg or '0'} from counters_collection where "
+                                  "counter_name=? order by dispatch_id", (ctr,)):
+        acc.setdefault(name, []).append((val, n))
+    batch = max([n for k, v in acc.items() if "k_spmm<" in k for _, n in v] or [0])
     out = {}
     for k, v in acc.items():
-        t = sorted(v[-last:])
-        out[k] = (t[len(t) // 2], len(v), max(v))
+        vals = [x for x, _ in v]
+        tail = v[-last:]
+        # only the merged tCG loop's two pose-tiled kernels are launched over agent ranges (the two colours' batches
+        # differ by a few tiles: within 10 % of the largest counts as the whole batch)
+        ranged = "k_spmm<" in k or "k_tcg_updir<" in k
+        if not ranged or batch <= 0 or min(n for _, n in tail) >= 0.9 * batch:
+            t = sorted(x for x, _ in tail)  # full-batch launches (or not a pose-tiled kernel)
+            out[k] = (t[len(t) // 2], len(v), max(vals), 1.0)
+            continue
+        tot = groups = 0.0
+        cnt = 0
+        for x, n in reversed(v):  # the last `last` batch equivalents
+            tot += x
+            groups += n
+            cnt += 1
+            if groups >= last * batch:
+                break
+        eq = groups / batch
+        out[k] = (tot / eq, len(v), max(vals), cnt / eq)
     return out
 
 
@@ -75,6 +112,7 @@ def summarize(outdir):
         rd = fetch[name][0] * 1024.0 * factor
         wr = write.get(name, (0.0, 0, 0.0))[0] * 1024.0
         kernels[mode] = {"kernel": name, "launches_profiled": fetch[name][1], "fetch_size_kb": fetch[name][0],
+                         "sub_launches_per_batch": fetch[name][3],
                          "write_size_kb": wr / 1024.0, "read_bytes_per_launch": rd, "write_bytes_per_launch": wr,
                          "traffic_bytes_per_launch": rd + wr}
     others = {}
@@ -84,7 +122,7 @@ def summarize(outdir):
         rd = fetch[name][0] * 1024.0 * factor
         wr = write.get(name, (0.0, 0, 0.0))[0] * 1024.0
         others[name.split("(")[0]] = {"read_bytes_per_launch": rd, "write_bytes_per_launch": wr,
-                                      "launches_profiled": fetch[name][1]}
+                                      "launches_profiled": fetch[name][1], "sub_launches_per_batch": fetch[name][3]}
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from dpgo_amd import hip as H  # the library the profiled bench loaded (no GPU call: the id is a constant)
     out = {"workload": "bench.py defaults (1M-pose grid, 64 agents, distributed init + burn-in, CG regime), "

@@ -40,6 +40,22 @@ def main():
     for nm, k, t, av in rows:
         print(f'"{nm}",{k},{t},{av:.1f},{100.0 * t / tot:.2f}')
     print(f"# kernel time total {tot / 1e6:.3f} ms")
+    # time with at least one kernel running (kernels on several streams overlap) and the gaps between kernels
+    busy = gaps = 0
+    longest = 0
+    end = None
+    for s, e in c.execute(f"select start, end from kernels {where} order by start"):
+        if end is None or s > end:
+            if end is not None:
+                gaps += 1
+                longest = max(longest, s - end)
+            busy += e - s
+            end = e
+        elif e > end:
+            busy += e - end
+            end = e
+    print(f"# busy (some kernel running) {busy / 1e6:.3f} ms; {gaps} gaps between kernels, the longest "
+          f"{longest / 1e3:.1f} us")
 
 
 if __name__ == "__main__":
