@@ -408,7 +408,12 @@ class Problem:
                                            enp, res))
         return [r.as_dict() for r in res] if want_results else None
 
+    def project_polar_dev(self, in_dev, out_dev):
+        """out = LiftedSEManifold::project(in) on device pointers, queued on the handle's stream."""
+        _check(lib().dpgo_hip_project_polar_dev(self.h, C.c_void_p(in_dev), C.c_void_p(out_dev)))
+
     def polar_combine_dev(self, A_dev, B_dev, ca, cb, out_dev):
+        """out = project(ca[k] A + cb[k] B) per agent k (B_dev None: project(ca[k] A)) on device pointers."""
         a, ap = _f64(ca)
         if B_dev is not None:
             b, bp = _f64(cb)

@@ -3,6 +3,21 @@ float64 implementations -- oracle and device -- are measured against (DESIGN.md 
 import numpy as np
 
 
+def gauss_jordan_inverse(M):
+    """M^-1 of one square block by Gauss-Jordan with partial pivoting in np.longdouble."""
+    L = np.longdouble
+    b = M.shape[0]
+    A = np.concatenate([np.asarray(M, dtype=L), np.eye(b, dtype=L)], axis=1)
+    for c in range(b):
+        piv = c + int(np.argmax(np.abs(A[c:, c])))
+        A[[c, piv]] = A[[piv, c]]
+        A[c] /= A[c, c]
+        for u in range(b):
+            if u != c:
+                A[u] -= A[u, c] * A[c]
+    return A[:, b:]
+
+
 def rtr_extended(Q, X0, d, tol, Delta0, Delta_max, max_iter, max_inner, precon="bj", return_state=False):
     """ROPTLIB RTR Run (A.4: tCG from eta = 0, QF retraction, rho test, radius update; G = 0) in extended precision
     (np.longdouble, 64-bit mantissa): the record sequence of _expected_records, as the reference trajectory the
@@ -47,16 +62,8 @@ def rtr_extended(Q, X0, d, tol, Delta0, Delta_max, max_iter, max_inner, precon="
     else:
         Minv = np.zeros((n, b, b), L)  # (Q_jj + 0.1 I)^-1 by Gauss-Jordan in extended precision
         for j in range(n):
-            A = np.concatenate([Qc[j * b:(j + 1) * b, j * b:(j + 1) * b].toarray().astype(L) +
-                                L(0.1) * np.eye(b, dtype=L), np.eye(b, dtype=L)], axis=1)
-            for c in range(b):
-                piv = c + int(np.argmax(np.abs(A[c:, c])))
-                A[[c, piv]] = A[[piv, c]]
-                A[c] /= A[c, c]
-                for u in range(b):
-                    if u != c:
-                        A[u] -= A[u, c] * A[c]
-            Minv[j] = A[:, b:]
+            Minv[j] = gauss_jordan_inverse(Qc[j * b:(j + 1) * b, j * b:(j + 1) * b].toarray().astype(L) +
+                                           L(0.1) * np.eye(b, dtype=L))
         psolve = lambda V: U(P(V) @ Minv)  # noqa: E731
 
     def proj(X, V):
