@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -2095,6 +2096,145 @@ int dpgo_hip_escape(dpgo_hip_problem h, const double* X, const double* v, double
   }
   if (!info->accepted) DPGO_TRY(lift_to_x2(nullptr, 0.0));
   return download(X_out, h->x2.p, h->vec_len(), h->stream);
+}
+
+// ----------------------------------------------------------------------- rank reduction
+namespace {
+int check_gram(int r, int d, long long n, const void* X, const void* C) {
+  if ((d != 2 && d != 3) || r < d || !dpgo::supported_rb(r, d + 1))
+    return fail(DPGO_HIP_EINVAL, "gram: unsupported (r, d)");
+  if (n <= 0) return fail(DPGO_HIP_EINVAL, "gram: need n >= 1 poses");
+  if (!X || !C) return fail(DPGO_HIP_EINVAL, "gram: null X or C");
+  return DPGO_HIP_OK;
+}
+
+bool ranges_overlap(const double* a, size_t na, const double* b, size_t nb) {
+  const auto pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+  return pa < pb + sizeof(double) * nb && pb < pa + sizeof(double) * na;
+}
+
+int check_rank_reduce(int r, int d, long long n, const double* X, int k, const double* W, const double* out) {
+  if ((d != 2 && d != 3) || r < d || !dpgo::supported_rb(r, d + 1))
+    return fail(DPGO_HIP_EINVAL, "rank_reduce: unsupported (r, d)");
+  if (k < d || k >= r) return fail(DPGO_HIP_EINVAL, "rank_reduce: need d <= k < r");
+  if (!dpgo::supported_rb(k, d + 1)) return fail(DPGO_HIP_EINVAL, "rank_reduce: unsupported (k, d)");
+  if (n <= 0) return fail(DPGO_HIP_EINVAL, "rank_reduce: need n >= 1 poses");
+  if (!X || !W || !out) return fail(DPGO_HIP_EINVAL, "rank_reduce: null X, W or X_out");
+  const size_t b = static_cast<size_t>(d) + 1;
+  if (ranges_overlap(X, r * b * n, out, k * b * n)) return fail(DPGO_HIP_EINVAL, "rank_reduce: X_out overlaps X");
+  return DPGO_HIP_OK;
+}
+}  // namespace
+
+long long dpgo_hip_gram_work_doubles(int r, int d, long long n) {
+  if ((d != 2 && d != 3) || r < d || !dpgo::supported_rb(r, d + 1) || n <= 0) return 0;
+  return dpgo::gram_work_doubles(r, static_cast<long>(n));
+}
+
+int dpgo_hip_gram_dev(int r, int d, long long n, const double* X_dev, double* C_dev, double* work_dev, void* stream) {
+  DPGO_TRY(check_gram(r, d, n, X_dev, C_dev));
+  if (!work_dev) return fail(DPGO_HIP_EINVAL, "gram: null work buffer (dpgo_hip_gram_work_doubles)");
+  if (usable_devices() == 0) return fail(DPGO_HIP_ENODEV, "no gfx950 device available (no CPU fallback)");
+  HIP_TRY(dpgo::launch_gram(r, d + 1, static_cast<long>(n), X_dev, C_dev, work_dev, static_cast<hipStream_t>(stream)));
+  return DPGO_HIP_OK;
+}
+
+int dpgo_hip_gram(int r, int d, int n, const double* X, double* C) {
+  DPGO_TRY(check_gram(r, d, n, X, C));
+  if (usable_devices() == 0) return fail(DPGO_HIP_ENODEV, "no gfx950 device available (no CPU fallback)");
+  const size_t rb = static_cast<size_t>(r) * (d + 1), rr = static_cast<size_t>(r) * r;
+  dpgo::DevBuf<double> x, cw;  // C, then the partials
+  HIP_TRY(x.ensure(rb * n));
+  HIP_TRY(cw.ensure(rr + static_cast<size_t>(dpgo::gram_work_doubles(r, n))));
+  hipStream_t s = nullptr;
+  HIP_TRY(hipMemcpyAsync(x.p, X, sizeof(double) * rb * n, hipMemcpyHostToDevice, s));
+  DPGO_TRY(dpgo_hip_gram_dev(r, d, n, x.p, cw.p, cw.p + rr, s));
+  return download(C, cw.p, rr, s);
+}
+
+int dpgo_hip_gram_eig(int r, const double* C, double* w, double* U) {
+  if (r < 1 || r > 8) return fail(DPGO_HIP_EINVAL, "gram_eig: need 1 <= r <= 8");
+  if (!C || !w || !U) return fail(DPGO_HIP_EINVAL, "gram_eig: null C, w or U");
+  double A[8][8], V[8][8];
+  for (int i = 0; i < r; ++i)
+    for (int j = 0; j < r; ++j) {
+      if (!std::isfinite(C[j * r + i])) return fail(DPGO_HIP_EINVAL, "gram_eig: C has a non-finite entry");
+      A[i][j] = 0.5 * (C[j * r + i] + C[i * r + j]);  // the symmetric part
+      V[i][j] = i == j ? 1.0 : 0.0;
+    }
+  // cyclic Jacobi: the rotation that annihilates A[p][q], row-cyclic sweeps until no off-diagonal entry moves a
+  // diagonal one (|a_pq| <= eps/8 min(|a_pp|, |a_qq|) counts as zero only when adding it changes neither)
+  for (int sweep = 0; sweep < 60; ++sweep) {
+    bool rotated = false;
+    for (int p = 0; p < r - 1; ++p)
+      for (int q = p + 1; q < r; ++q) {
+        const double apq = A[p][q];
+        if (apq == 0.0) continue;
+        const double g = 100.0 * std::fabs(apq);
+        if (sweep > 3 && std::fabs(A[p][p]) + g == std::fabs(A[p][p]) && std::fabs(A[q][q]) + g == std::fabs(A[q][q])) {
+          A[p][q] = A[q][p] = 0.0;
+          continue;
+        }
+        rotated = true;
+        const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
+        const double t = std::isinf(theta) ? 0.0 : std::copysign(1.0, theta) / (std::fabs(theta) + std::hypot(1.0, theta));
+        const double c = 1.0 / std::sqrt(1.0 + t * t), s = t * c;
+        for (int k = 0; k < r; ++k) {  // A <- A J
+          const double akp = A[k][p], akq = A[k][q];
+          A[k][p] = c * akp - s * akq;
+          A[k][q] = s * akp + c * akq;
+        }
+        for (int k = 0; k < r; ++k) {  // A <- J^T A
+          const double apk = A[p][k], aqk = A[q][k];
+          A[p][k] = c * apk - s * aqk;
+          A[q][k] = s * apk + c * aqk;
+        }
+        A[p][q] = A[q][p] = 0.0;
+        for (int k = 0; k < r; ++k) {
+          const double vkp = V[k][p], vkq = V[k][q];
+          V[k][p] = c * vkp - s * vkq;
+          V[k][q] = s * vkp + c * vkq;
+        }
+      }
+    if (!rotated) break;
+  }
+  int order[8];
+  for (int i = 0; i < r; ++i) order[i] = i;
+  std::stable_sort(order, order + r, [&](int a, int b) { return A[a][a] > A[b][b]; });
+  for (int i = 0; i < r; ++i) {
+    const int c = order[i];
+    w[i] = A[c][c];
+    int big = 0;  // sign convention: the column's largest-magnitude entry (the first of equals) is positive
+    for (int k = 1; k < r; ++k)
+      if (std::fabs(V[k][c]) > std::fabs(V[big][c])) big = k;
+    const double sgn = V[big][c] < 0.0 ? -1.0 : 1.0;
+    for (int k = 0; k < r; ++k) U[i * r + k] = sgn * V[k][c];
+  }
+  return DPGO_HIP_OK;
+}
+
+int dpgo_hip_rank_reduce_dev(int r, int d, long long n, const double* X_dev, int k, const double* W, double* X_out_dev,
+                             void* stream) {
+  DPGO_TRY(check_rank_reduce(r, d, n, X_dev, k, W, X_out_dev));
+  if (usable_devices() == 0) return fail(DPGO_HIP_ENODEV, "no gfx950 device available (no CPU fallback)");
+  dpgo::RankW w{};
+  std::memcpy(w.v, W, sizeof(double) * r * k);
+  HIP_TRY(dpgo::launch_rank_project(r, k, d + 1, static_cast<long>(n), X_dev, w, X_out_dev,
+                                    static_cast<hipStream_t>(stream)));
+  return DPGO_HIP_OK;
+}
+
+int dpgo_hip_rank_reduce(int r, int d, int n, const double* X, int k, const double* W, double* X_out) {
+  DPGO_TRY(check_rank_reduce(r, d, n, X, k, W, X_out));
+  if (usable_devices() == 0) return fail(DPGO_HIP_ENODEV, "no gfx950 device available (no CPU fallback)");
+  const size_t b = static_cast<size_t>(d) + 1, rb = r * b, kb = k * b;
+  dpgo::DevBuf<double> x, o;
+  HIP_TRY(x.ensure(rb * n));
+  HIP_TRY(o.ensure(kb * n));
+  hipStream_t s = nullptr;
+  HIP_TRY(hipMemcpyAsync(x.p, X, sizeof(double) * rb * n, hipMemcpyHostToDevice, s));
+  DPGO_TRY(dpgo_hip_rank_reduce_dev(r, d, n, x.p, k, W, o.p, s));
+  return download(X_out, o.p, kb * n, s);
 }
 
 // ----------------------------------------------------------------------- certification

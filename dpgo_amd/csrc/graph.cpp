@@ -709,3 +709,55 @@ int dpgo_graph_escape(dpgo_graph g, int r, const double* X, const double* eigvec
                                 g->tau.data(), w.data()));
   return dpgo_hip_escape(h, X, v.data(), lambda_min, params, X_out, info);
 }
+
+// The staircase's way down on the whole graph (build-defined): Gram -> spectrum -> numerical rank ->
+// reduce, X on the device once; f before and after through the central unit-weight handles of rank r and k.
+int dpgo_graph_rank_reduce(dpgo_graph g, int r, const double* X, double tol, int* k_out, double* X_out,
+                           dpgo_rank_info* info) {
+  if (!g || !X || !k_out || !X_out || !info) return fail(DPGO_HIP_EINVAL, "rank_reduce: null argument");
+  if (!(tol >= 0.0 && tol < 1.0)) return fail(DPGO_HIP_EINVAL, "rank_reduce: tol must lie in [0, 1)");
+  const int d = g->d, n = g->n, m = static_cast<int>(g->p1.size());
+  if (r < d || !dpgo::supported_rb(r, d + 1)) return fail(DPGO_HIP_EINVAL, "rank_reduce: unsupported (r, d)");
+  if (usable_devices() == 0) return fail(DPGO_HIP_ENODEV, "no gfx950 device available (no CPU fallback)");
+  const size_t b = static_cast<size_t>(d) + 1, rr = static_cast<size_t>(r) * r;
+  const std::vector<double> wgt(static_cast<size_t>(m), 1.0);
+  auto f_at = [&](int rank, const double* Xr, double* f) -> int {
+    dpgo_hip_problem h = nullptr;
+    DPGO_TRY(dpgo_hip_problem_create(n, d, rank, &h));
+    struct Guard {
+      dpgo_hip_problem h;
+      ~Guard() { dpgo_hip_problem_destroy(h); }
+    } guard{h};
+    DPGO_TRY(dpgo_hip_set_Q_edges(h, 0, m, g->p1.data(), g->p2.data(), g->R.data(), g->t.data(), g->kappa.data(),
+                                  g->tau.data(), wgt.data()));
+    return dpgo_hip_f(h, Xr, f);
+  };
+  dpgo::DevBuf<double> x, cw, o;
+  HIP_TRY(x.ensure(r * b * n));
+  HIP_TRY(cw.ensure(rr + static_cast<size_t>(dpgo::gram_work_doubles(r, n))));
+  hipStream_t s = nullptr;
+  HIP_TRY(hipMemcpyAsync(x.p, X, sizeof(double) * r * b * n, hipMemcpyHostToDevice, s));
+  DPGO_TRY(dpgo_hip_gram_dev(r, d, n, x.p, cw.p, cw.p + rr, s));
+  double C[64], U[64];
+  HIP_TRY(hipMemcpyAsync(C, cw.p, sizeof(double) * rr, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  for (double& wi : info->w) wi = std::nan("");
+  DPGO_TRY(dpgo_hip_gram_eig(r, C, info->w, U));
+  int k = 0;
+  for (int i = 0; i < r; ++i) k += info->w[i] > tol * info->w[0] ? 1 : 0;
+  k = std::max(k, d);
+  *k_out = k;
+  info->dropped = 0.0;
+  for (int i = r - 1; i >= k; --i) info->dropped += info->w[i];
+  DPGO_TRY(f_at(r, X, &info->f_before));
+  if (k == r) {
+    std::memmove(X_out, X, sizeof(double) * r * b * n);
+    info->f_after = info->f_before;
+    return DPGO_HIP_OK;
+  }
+  HIP_TRY(o.ensure(k * b * n));
+  DPGO_TRY(dpgo_hip_rank_reduce_dev(r, d, n, x.p, k, U, o.p, s));
+  HIP_TRY(hipMemcpyAsync(X_out, o.p, sizeof(double) * k * b * n, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return f_at(k, X_out, &info->f_after);
+}

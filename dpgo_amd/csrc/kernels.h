@@ -457,6 +457,22 @@ hipError_t launch_frame_lift(int r, int b, long n, const double* T, const FrameL
 // r + 1 must be compiled (hipErrorInvalidValue for r = 8); out must not overlap X.
 hipError_t launch_lift_escape(int r, int b, long n, const double* X, const double* v, double alpha, double* out,
                               hipStream_t stream);
+// Rank reduction (build-defined).  Gram of the rotation columns, C = sum_j Y_j Y_j^T
+// (r x r, written full symmetric, column-major): kGramSpans consecutive 64-pose spans per block, one partial of
+// r (r + 1) / 2 packed sums per block in `work` (gram_work_doubles(r, n) doubles), then one finishing launch that
+// sums the partials in a fixed order.  No atomics: C is a function of (X, n) alone, whatever the pointer alignment.
+constexpr int kGramSpans = 2;
+inline long gram_blocks(long n) { return (n + 64L * kGramSpans - 1) / (64L * kGramSpans); }
+inline long gram_work_doubles(int r, long n) { return gram_blocks(n) * (r * (r + 1) / 2); }
+hipError_t launch_gram(int r, int b, long n, const double* X, double* C, double* work, hipStream_t stream);
+// out_j (k x b per pose) = [polar(W^T Y_j) | W^T p_j] of the n lifted poses X (r x b per pose), W r x k column-major
+// in the kernel arguments, b - 1 <= k < r; polar is polar_fast (LiftedSEManifold::project).  No tile set: any
+// n >= 1; out must not overlap X.
+struct RankW {
+  double v[56];  // r x k column-major, k < r <= 8
+};
+hipError_t launch_rank_project(int r, int k, int b, long n, const double* X, const RankW& W, double* out,
+                               hipStream_t stream);
 // PGOAgent::computeConvergedLoopClosureRatio (src/PGOAgent.cpp:1247-1289): per agent a, the share of
 // its loop closures idx[off[a] .. off[a+1]) whose weight w[] is exactly 1 or 0 (0/0 = NaN, as there)
 hipError_t launch_conv_ratio(int num_agents, const int* off, const int* idx, const double* w, double* ratio,

@@ -2911,6 +2911,194 @@ __global__ __launch_bounds__(64) void k_frame_lift(long n, const double* __restr
   }
 }
 
+// Rank reduction, first half (build-defined): the Gram matrix of the rotation columns,
+//   C = sum_j Y_j Y_j^T   (R x R; the translation column takes no part),
+// as R (R + 1) / 2 packed sums (a <= c at index c (c + 1) / 2 + a).  Block k takes the kGramSpans consecutive 64-pose
+// spans from pose 64 kGramSpans k on; each span streams through LDS exactly as k_round_se stages it (16-byte chunks on
+// a full, aligned span, 8-byte otherwise: the staging moves bits only, so the sums do not depend on the alignment),
+// thread t adds its pose's products -- each one a product and D - 1 FMAs, then one addition into the thread's sum --
+// and after the last span one xor butterfly over the 64 lanes (five DPP / permute steps and one across the halves per
+// packed entry, the same order in every lane) leaves the block's partial, which lane 0 writes.  The grid is a
+// function of n alone; k_gram_finish sums the partials.  No atomics anywhere.
+template <int R, int B>
+__global__ __launch_bounds__(64) void k_gram(long n, const double* __restrict__ X, double* __restrict__ partial) {
+  constexpr int D = B - 1;
+  constexpr int PW = R * B, PS = PW | 1;
+  constexpr int P = R * (R + 1) / 2;
+  __shared__ double sm[64 * PS];
+  const int t = static_cast<int>(threadIdx.x);
+  double acc[P];
+#pragma unroll
+  for (int i = 0; i < P; ++i) acc[i] = 0.0;
+#pragma unroll 1
+  for (int s = 0; s < kGramSpans; ++s) {
+    const long first = (static_cast<long>(blockIdx.x) * kGramSpans + s) * 64;
+    if (first >= n) break;  // block-uniform
+    const int count = n - first < 64 ? static_cast<int>(n - first) : 64;
+    const double* src = X + first * PW;
+    if (s > 0) __syncthreads();  // the previous span has been read
+    if (PW % 2 == 0 && count == 64 && (reinterpret_cast<unsigned long>(src) & 15) == 0) {
+      constexpr int NV = PW / 2;  // 16-byte chunks per lane (PW even: a chunk never straddles two poses)
+      const double2* S2 = reinterpret_cast<const double2*>(src);
+      double2 v[NV];
+#pragma unroll
+      for (int i = 0; i < NV; ++i) v[i] = S2[t + 64 * i];
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        const int x = 2 * (t + 64 * i);
+        double* q = sm + (x / PW) * PS + x % PW;
+        q[0] = v[i].x;
+        q[1] = v[i].y;
+      }
+    } else {
+      const int total = count * PW;
+      for (int x = t; x < total; x += 64) sm[(x / PW) * PS + x % PW] = src[x];
+    }
+    __syncthreads();
+    if (t < count) {
+      const double* ps = sm + t * PS;
+      double Y[R][D];
+#pragma unroll
+      for (int c = 0; c < D; ++c)
+#pragma unroll
+        for (int a = 0; a < R; ++a) Y[a][c] = ps[c * R + a];
+#pragma unroll
+      for (int c = 0; c < R; ++c)
+#pragma unroll
+        for (int a = 0; a <= c; ++a) {
+          double p = Y[a][0] * Y[c][0];
+#pragma unroll
+          for (int q = 1; q < D; ++q) p = fma(Y[a][q], Y[c][q], p);
+          acc[c * (c + 1) / 2 + a] += p;
+        }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < P; ++i) {
+    double v = acc[i];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    acc[i] = v;
+  }
+  if (t == 0) {  // entry-major: k_gram_finish reads each entry's partials contiguously
+    double* dst = partial + blockIdx.x;
+#pragma unroll
+    for (int i = 0; i < P; ++i) dst[static_cast<long>(i) * gridDim.x] = acc[i];
+  }
+}
+
+// Second half of the Gram: block i sums packed entry i of the `blocks` partials (entry-major: partial[i blocks + g]
+// is block g's) -- thread t adds partials t, t + 1024, ... in that order, k_gram's butterfly sums each wave, and
+// thread 0 adds the 16 wave sums in wave order -- and writes it at both (a, c) and (c, a) of the full column-major C.
+// The order is a function of `blocks` alone: bitwise repeatable.
+constexpr int kGramFinishThreads = 1024;
+__global__ __launch_bounds__(kGramFinishThreads) void k_gram_finish(long blocks, int R,
+                                                                    const double* __restrict__ partial,
+                                                                    double* __restrict__ C) {
+  __shared__ double ws[kGramFinishThreads / 64];
+  const int i = static_cast<int>(blockIdx.x);
+  const int t = static_cast<int>(threadIdx.x);
+  const double* src = partial + static_cast<long>(i) * blocks;
+  double v = 0.0;
+  for (long g = t; g < blocks; g += kGramFinishThreads) v += src[g];
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+  if ((t & 63) == 0) ws[t >> 6] = v;
+  __syncthreads();
+  if (t == 0) {
+    double s = ws[0];
+#pragma unroll
+    for (int k = 1; k < kGramFinishThreads / 64; ++k) s += ws[k];
+    int c = 0;
+    while ((c + 1) * (c + 2) / 2 <= i) ++c;
+    const int a = i - c * (c + 1) / 2;
+    C[c * R + a] = s;
+    C[a * R + c] = s;
+  }
+}
+
+// Rank reduction, second half: truncate the n poses X (R x B each) to rank K < R along W (R x K, orthonormal columns:
+// the leading eigenvectors of k_gram's C), per pose
+//   out_j = [polar(W^T Y_j) | W^T p_j],   K x B column-major,
+// polar being LiftedSEManifold::project's factor (polar_fast: Newton-Schulz near the manifold, else polar_inplace's
+// one-sided Jacobi).  A pose whose W^T Y_j is exactly rank-deficient takes the Jacobi path, whose zero columns stay
+// zero (1 / sigma is replaced by 0): the output is finite and not orthonormal; that pose has no nearest point and
+// the pass does not invent one.  k_round_se's shape: block k takes poses [64 k, 64 k + 64); the R B-wide span streams
+// in through LDS coalesced (16-byte chunks where the span width is even, the block full and the span aligned, 8-byte
+// otherwise), thread t works on pose t, and the K B-wide result streams out of the same LDS.  Row strides are the
+// span widths made odd (conflict-free b64 reads).  W travels in the kernel arguments.
+template <int R, int K, int B>
+__global__ __launch_bounds__(64) void k_rank_project(long n, const double* __restrict__ X, RankW w,
+                                                     double* __restrict__ out) {
+  constexpr int D = B - 1;
+  constexpr int PW = R * B, PS = PW | 1;
+  constexpr int OW = K * B, OS = OW | 1;
+  static_assert(D <= K && K < R && OS <= PS, "the reduced poses reuse the staged span's LDS");
+  __shared__ double sm[64 * PS];
+  const int t = static_cast<int>(threadIdx.x);
+  const long first = static_cast<long>(blockIdx.x) * 64;
+  if (first >= n) return;
+  const int count = n - first < 64 ? static_cast<int>(n - first) : 64;
+  const double* src = X + first * PW;
+  double* dst = out + first * OW;
+  const bool full = count == 64;
+  if (PW % 2 == 0 && full && (reinterpret_cast<unsigned long>(src) & 15) == 0) {
+    constexpr int NV = PW / 2;  // 16-byte chunks per lane (PW even: a chunk never straddles two poses)
+    const double2* S2 = reinterpret_cast<const double2*>(src);
+    double2 v[NV];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) v[i] = S2[t + 64 * i];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int x = 2 * (t + 64 * i);
+      double* q = sm + (x / PW) * PS + x % PW;
+      q[0] = v[i].x;
+      q[1] = v[i].y;
+    }
+  } else {
+    const int total = count * PW;
+    for (int x = t; x < total; x += 64) sm[(x / PW) * PS + x % PW] = src[x];
+  }
+  __syncthreads();
+  const bool own = t < count;
+  double M[K][B];
+  if (own) {
+    const double* ps = sm + t * PS;
+#pragma unroll
+    for (int c = 0; c < B; ++c)
+#pragma unroll
+      for (int i = 0; i < K; ++i) {
+        double s = 0.0;
+#pragma unroll
+        for (int a = 0; a < R; ++a) s = fma(w.v[i * R + a], ps[c * R + a], s);
+        M[i][c] = s;
+      }
+  }
+  __syncthreads();  // every pose of the span is in registers: its LDS now takes the reduced poses
+  if (own) {
+    polar_fast<K, D>(M);  // the translation column passes through unchanged
+    double* po = sm + t * OS;
+#pragma unroll
+    for (int c = 0; c < B; ++c)
+#pragma unroll
+      for (int i = 0; i < K; ++i) po[c * K + i] = M[i][c];
+  }
+  __syncthreads();
+  if (OW % 2 == 0 && full && (reinterpret_cast<unsigned long>(dst) & 15) == 0) {
+    constexpr int NO = OW / 2;
+    double2* O2 = reinterpret_cast<double2*>(dst);
+#pragma unroll
+    for (int i = 0; i < NO; ++i) {
+      const int x = 2 * (t + 64 * i);
+      const double* q = sm + (x / OW) * OS + x % OW;
+      O2[t + 64 * i] = make_double2(q[0], q[1]);
+    }
+  } else {
+    const int total_out = count * OW;
+    for (int x = t; x < total_out; x += 64) dst[x] = sm[(x / OW) * OS + x % OW];
+  }
+}
+
 // Nesterov updateV deferred into the colour's next combination pass (one pass instead of two):
 //   V' = project(V + gv (X - Yv))   (updateV, src/PGOAgent.cpp:1086-1091, of the agent's last update)
 //   out = project(sa X + sb V')     (updateY / the iterate(false) step, :1077-1084, of the next iteration)
@@ -5242,6 +5430,57 @@ hipError_t launch_frame_lift(int r, int b, long n, const double* T, const FrameL
   const dim3 grid(static_cast<unsigned>(blocks));
   DPGO_DISPATCH(r, b, (k_frame_lift<R, B><<<grid, 64, 0, stream>>>(n, T, ylift, frames, frame_of, out)));
   return hipGetLastError();
+}
+
+hipError_t launch_gram(int r, int b, long n, const double* X, double* C, double* work, hipStream_t stream) {
+  if (n <= 0 || X == nullptr || C == nullptr || work == nullptr) return hipErrorInvalidValue;
+  const long blocks = gram_blocks(n);
+  if (blocks > 0x7fffffffL) return hipErrorInvalidValue;
+  const dim3 grid(static_cast<unsigned>(blocks));
+  DPGO_DISPATCH(r, b, (k_gram<R, B><<<grid, 64, 0, stream>>>(n, X, work)));
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  k_gram_finish<<<r * (r + 1) / 2, kGramFinishThreads, 0, stream>>>(blocks, r, work, C);
+  return hipGetLastError();
+}
+
+namespace {
+// the input ranks K < R <= 8 of one compiled output shape (K, B)
+template <int R, int K, int B>
+hipError_t rank_project_rkb(dim3 grid, long n, const double* X, const RankW& W, double* out, hipStream_t stream) {
+  if constexpr (R > K) {
+    k_rank_project<R, K, B><<<grid, 64, 0, stream>>>(n, X, W, out);
+    return hipSuccess;
+  } else {
+    return hipErrorInvalidValue;
+  }
+}
+template <int K, int B>
+hipError_t rank_project_kb(int r, dim3 grid, long n, const double* X, const RankW& W, double* out,
+                           hipStream_t stream) {
+  switch (r) {
+    case 3: return rank_project_rkb<3, K, B>(grid, n, X, W, out, stream);
+    case 4: return rank_project_rkb<4, K, B>(grid, n, X, W, out, stream);
+    case 5: return rank_project_rkb<5, K, B>(grid, n, X, W, out, stream);
+    case 6: return rank_project_rkb<6, K, B>(grid, n, X, W, out, stream);
+    case 7: return rank_project_rkb<7, K, B>(grid, n, X, W, out, stream);
+    case 8: return rank_project_rkb<8, K, B>(grid, n, X, W, out, stream);
+    default: return hipErrorInvalidValue;
+  }
+}
+}  // namespace
+
+hipError_t launch_rank_project(int r, int k, int b, long n, const double* X, const RankW& W, double* out,
+                               hipStream_t stream) {
+  if (n <= 0 || X == nullptr || out == nullptr || k < b - 1 || k >= r || !supported_rb(r, b))
+    return hipErrorInvalidValue;
+  const long blocks = (n + 63) / 64;
+  if (blocks > 0x7fffffffL) return hipErrorInvalidValue;
+  const dim3 grid(static_cast<unsigned>(blocks));
+  // R is the output rank here: the dispatch runs over the 13 compiled (k, b)
+  hipError_t e = hipSuccess;
+  DPGO_DISPATCH(k, b, (e = rank_project_kb<R, B>(r, grid, n, X, W, out, stream)));
+  return e != hipSuccess ? e : hipGetLastError();
 }
 
 hipError_t launch_sqdiff(int r, int b, const LaunchCtx& c, const double* A, const double* Bv) {

@@ -125,6 +125,8 @@ struct dpgo_rbcd_s {
   int n_global = 0;
   std::vector<int> own_of_global;  // global pose id -> owned buffer pose index, -1 = another rank's
   DevBuf<double> Tround;           // the owned poses rounded to SE(d), d x b per pose
+  // rank reduction (dpgo_rbcd_gram / _get_X_reduced): C then k_gram's partials; the owned poses at rank k
+  DevBuf<double> gram_cw, Xreduced;
   // trajectory read-in (dpgo_rbcd_set_trajectory): the owned poses' d x b blocks, then the K frames, staged for
   // k_frame_lift; the owned poses' global agent ids, built at the first call with frames
   DevBuf<double> Tin;
@@ -955,6 +957,37 @@ int dpgo_rbcd_get_trajectory(dpgo_rbcd e, const double* anchor, double* Tg) {
   HIP_TRY(hipStreamSynchronize(e->stream));
   for (long q = 0; q < e->Nown; ++q)
     std::memcpy(Tg + static_cast<size_t>(e->own_global[q]) * dbs, &host[q * dbs], sizeof(double) * dbs);
+  return DPGO_HIP_OK;
+}
+
+int dpgo_rbcd_gram(dpgo_rbcd e, double* C) {
+  if (!e || !C) return fail(DPGO_HIP_EINVAL, "null argument");
+  const size_t rr = static_cast<size_t>(e->r) * e->r;
+  if (e->Nown == 0) {  // a rank without poses contributes nothing to the sum
+    std::fill(C, C + rr, 0.0);
+    return DPGO_HIP_OK;
+  }
+  DPGO_TRY(join_side(e));
+  HIP_TRY(e->gram_cw.ensure(rr + static_cast<size_t>(dpgo::gram_work_doubles(e->r, e->Nown))));
+  DPGO_TRY(dpgo_hip_gram_dev(e->r, e->d, e->Nown, e->X.p, e->gram_cw.p, e->gram_cw.p + rr, e->stream));
+  HIP_TRY(hipMemcpyAsync(C, e->gram_cw.p, sizeof(double) * rr, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return DPGO_HIP_OK;
+}
+
+int dpgo_rbcd_get_X_reduced(dpgo_rbcd e, int k, const double* W, double* Xk) {
+  if (!e || !W || !Xk) return fail(DPGO_HIP_EINVAL, "null argument");
+  if (k < e->d || k >= e->r) return fail(DPGO_HIP_EINVAL, "get_X_reduced: need d <= k < r");
+  if (e->Nown == 0) return DPGO_HIP_OK;
+  DPGO_TRY(join_side(e));
+  const size_t kbs = static_cast<size_t>(k) * e->b;
+  HIP_TRY(e->Xreduced.ensure(static_cast<size_t>(e->Nown) * kbs));
+  DPGO_TRY(dpgo_hip_rank_reduce_dev(e->r, e->d, e->Nown, e->X.p, k, W, e->Xreduced.p, e->stream));
+  std::vector<double> host(static_cast<size_t>(e->Nown) * kbs);
+  HIP_TRY(hipMemcpyAsync(host.data(), e->Xreduced.p, sizeof(double) * host.size(), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  for (long q = 0; q < e->Nown; ++q)
+    std::memcpy(Xk + static_cast<size_t>(e->own_global[q]) * kbs, &host[q * kbs], sizeof(double) * kbs);
   return DPGO_HIP_OK;
 }
 

@@ -57,6 +57,11 @@ class EscapeInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class RankInfo(C.Structure):
+    """dpgo_rank_info (include/dpgo_rbcd.h)."""
+    _fields_ = [("w", C.c_double * 8), ("dropped", C.c_double), ("f_before", C.c_double), ("f_after", C.c_double)]
+
+
 class DPGOHipError(RuntimeError):
     pass
 
@@ -102,6 +107,13 @@ _SIGS = [
     ("dpgo_hip_escape_direction", [C.c_int, C.c_int, C.c_int, _dp, _dp], C.c_int),
     ("dpgo_hip_default_escape_params", [C.POINTER(EscapeParams)], None),
     ("dpgo_hip_escape", [C.c_void_p, _dp, _dp, C.c_double, C.POINTER(EscapeParams), _dp, C.POINTER(EscapeInfo)],
+     C.c_int),
+    ("dpgo_hip_gram", [C.c_int, C.c_int, C.c_int, _dp, _dp], C.c_int),
+    ("dpgo_hip_gram_work_doubles", [C.c_int, C.c_int, C.c_longlong], C.c_longlong),
+    ("dpgo_hip_gram_dev", [C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    ("dpgo_hip_gram_eig", [C.c_int, _dp, _dp, _dp], C.c_int),
+    ("dpgo_hip_rank_reduce", [C.c_int, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp], C.c_int),
+    ("dpgo_hip_rank_reduce_dev", [C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_int, _dp, C.c_void_p, C.c_void_p],
      C.c_int),
     ("dpgo_hip_optimize", [C.c_void_p, C.POINTER(OptParams), _dp, _dp, C.POINTER(OptResult)], C.c_int),
     ("dpgo_hip_f_dev", [C.c_void_p, C.c_void_p, _dp], C.c_int),
@@ -641,6 +653,75 @@ def escape_direction(vec, d):
     return out
 
 
+def gram(X, d):
+    """C = sum_j Y_j Y_j^T (r x r) over the rotation columns of the lifted poses X (r x (d+1) n), on the device: a
+    function of (X, n) alone, bitwise repeatable."""
+    r = X.shape[0]
+    n = X.shape[1] // (d + 1)
+    x, xp = _f64(to_dev_layout(X))
+    o = np.empty(r * r)
+    _check(lib().dpgo_hip_gram(r, d, n, xp, o.ctypes.data_as(_dp)))
+    return o.reshape(r, r).T.copy()
+
+
+def gram_work_doubles(r, d, n) -> int:
+    """doubles of the work buffer gram_dev needs."""
+    return int(lib().dpgo_hip_gram_work_doubles(int(r), int(d), int(n)))
+
+
+def gram_dev(r, d, n, X_dev: int, C_dev: int, work_dev: int, stream_ptr: int | None = None):
+    """gram on device pointers (C_dev: r r doubles, column-major; work_dev: gram_work_doubles), queued on `stream_ptr`
+    (None = the null stream) without synchronisation."""
+    _check(lib().dpgo_hip_gram_dev(int(r), int(d), int(n), C.c_void_p(X_dev), C.c_void_p(C_dev), C.c_void_p(work_dev),
+                                   C.c_void_p(stream_ptr or 0)))
+
+
+def gram_eig(Cm):
+    """(w, U) of the symmetric r x r matrix Cm (r <= 8) by cyclic Jacobi: w descending, U's columns the eigenvectors,
+    each with its largest-magnitude entry positive.  Host only."""
+    Cm = np.asarray(Cm, dtype=np.float64)
+    if Cm.ndim != 2 or Cm.shape[0] != Cm.shape[1]:
+        raise DPGOHipError("gram_eig: C must be square")
+    r = Cm.shape[0]
+    c, cp = _f64(Cm.T.ravel())
+    w = np.empty(max(r, 1))
+    U = np.empty(max(r * r, 1))
+    _check(lib().dpgo_hip_gram_eig(r, cp, w.ctypes.data_as(_dp), U.ctypes.data_as(_dp)))
+    return w[:r].copy(), U[:r * r].reshape(r, r).T.copy()
+
+
+def numerical_rank(w, d, tol):
+    """k = max(d, #{i : w_i > tol w_1}) of a descending spectrum w."""
+    w = np.asarray(w)
+    return max(int(d), int(np.count_nonzero(w > tol * w[0])))
+
+
+def _w_colmajor(W, r):
+    W = np.asarray(W, dtype=np.float64)
+    if W.ndim != 2 or W.shape[0] != r:
+        raise DPGOHipError(f"W must be r x k with r = {r}")
+    return W.shape[1], _f64(W.T.ravel())
+
+
+def rank_reduce(X, d, W):
+    """X truncated to rank k along W (r x k, orthonormal columns): per pose [polar(W^T Y_j) | W^T p_j], k x (d+1) n."""
+    r = X.shape[0]
+    n = X.shape[1] // (d + 1)
+    k, (w, wp) = _w_colmajor(W, r)
+    x, xp = _f64(to_dev_layout(X))
+    o = np.empty(max(n * k * (d + 1), 1))
+    _check(lib().dpgo_hip_rank_reduce(r, d, n, xp, k, wp, o.ctypes.data_as(_dp)))
+    return from_dev_layout(o, k)
+
+
+def rank_reduce_dev(r, d, n, X_dev: int, W, X_out_dev: int, stream_ptr: int | None = None):
+    """rank_reduce on device pointers (W: the host r x k matrix), queued on `stream_ptr` (None = the null stream)
+    without synchronisation."""
+    k, (w, wp) = _w_colmajor(W, int(r))
+    _check(lib().dpgo_hip_rank_reduce_dev(int(r), int(d), int(n), C.c_void_p(X_dev), k, wp, C.c_void_p(X_out_dev),
+                                          C.c_void_p(stream_ptr or 0)))
+
+
 # ----------------------------------------------------------------------------------------
 # Pose graphs + multi-agent RBCD engine (include/dpgo_rbcd.h)
 # ----------------------------------------------------------------------------------------
@@ -697,6 +778,9 @@ _SIGS2 = [
                                _dp, C.c_void_p], C.c_int),
     ("dpgo_graph_escape", [C.c_void_p, C.c_int, _dp, _dp, C.c_int, C.c_double, C.POINTER(EscapeParams), _dp,
                            C.POINTER(EscapeInfo)], C.c_int),
+    ("dpgo_graph_rank_reduce", [C.c_void_p, C.c_int, _dp, C.c_double, _ip, _dp, C.POINTER(RankInfo)], C.c_int),
+    ("dpgo_rbcd_gram", [C.c_void_p, _dp], C.c_int),
+    ("dpgo_rbcd_get_X_reduced", [C.c_void_p, C.c_int, _dp, _dp], C.c_int),
     ("dpgo_chordal_initialization_gpu", [C.c_int, C.c_int, C.c_int, _ip, _ip, _dp, _dp, _dp, _dp, C.c_double,
                                          C.c_int, _dp, _ip, _dp], C.c_int),
     ("dpgo_graph_chordal_init_gpu", [C.c_void_p, C.c_int, _dp, C.c_double, C.c_int, _dp, _ip, _dp], C.c_int),
@@ -949,6 +1033,23 @@ class Graph:
                                        out.ctypes.data_as(_dp), C.byref(info)))
         return out, info.as_dict()
 
+    def rank_reduce(self, X, r, tol):
+        """The staircase's way down: X (flat r x (d+1) n column-major buffer, or the matrix) truncated to its
+        numerical rank k = max(d, #{i : w_i > tol w_1}) of the rotation Gram's spectrum w.  Returns (k, X_out flat
+        k x (d+1) n column-major, ready for Rbcd.set_X at rank k; info dict(w [r], dropped, f_before, f_after)).
+        k = r: X_out is a copy of X."""
+        X = np.asarray(X, dtype=np.float64)
+        flat = np.ascontiguousarray(X.T).ravel() if X.ndim == 2 else np.ascontiguousarray(X).ravel()
+        bn = (self.d + 1) * self.n
+        if flat.size != r * bn:
+            raise DPGOHipError("X has the wrong size")
+        out = np.empty(r * bn)
+        k, info = C.c_int(), RankInfo()
+        _check(lib().dpgo_graph_rank_reduce(self.h, int(r), flat.ctypes.data_as(_dp), float(tol), C.byref(k),
+                                            out.ctypes.data_as(_dp), C.byref(info)))
+        return k.value, out[:k.value * bn].copy(), dict(w=np.array(info.w[:r]), dropped=info.dropped,
+                                                        f_before=info.f_before, f_after=info.f_after)
+
     def grid_partition(self, agents_per_axis):
         out = np.empty(self.n, np.int32)
         _check(lib().dpgo_graph_grid_partition(self.h, int(agents_per_axis), out.ctypes.data_as(_ip)))
@@ -1161,6 +1262,25 @@ class Rbcd:
             if a.size != self.params.r * (self.graph.d + 1):
                 raise ValueError("anchor must be r x (d+1)")
         _check(lib().dpgo_rbcd_get_trajectory(self.h, ap, T_flat.ctypes.data_as(_dp)))
+
+    def gram(self):
+        """This rank's partial Gram sum_j Y_j Y_j^T (r x r) over its owned poses, from the engine's X on the device;
+        with several ranks the caller sums the partials."""
+        r = self.params.r
+        o = np.empty(r * r)
+        _check(lib().dpgo_rbcd_gram(self.h, o.ctypes.data_as(_dp)))
+        return o.reshape(r, r).T.copy()
+
+    def get_X_reduced_into(self, W, Xk_flat):
+        """The engine's X truncated to rank k along W (r x k; hip.rank_reduce's pass on the device), written at the
+        owned poses of a global flat k x (d+1) n column-major host array (from_dev_layout(Xk_flat, k) is the
+        matrix; Rbcd.set_X of a rank-k engine takes it)."""
+        assert Xk_flat.dtype == np.float64 and Xk_flat.flags.c_contiguous
+        k, (w, wp) = _w_colmajor(W, self.params.r)
+        need = self.graph.n * (self.graph.d + 1) * k
+        if Xk_flat.size < need:
+            raise ValueError(f"X buffer holds {Xk_flat.size} doubles, rank {k} needs {need}")
+        _check(lib().dpgo_rbcd_get_X_reduced(self.h, k, wp, Xk_flat.ctypes.data_as(_dp)))
 
     def weights_into(self, w):
         """Current weight of every measurement this rank is responsible for (weight_owner's agent lives here), at

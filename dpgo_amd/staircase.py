@@ -3,7 +3,8 @@
 At each rank r the engine runs its colour schedule to a critical point, the whole-graph certificate
 (Graph.certify) decides whether it is the global optimum of the relaxation, and if not Graph.escape moves off the
 saddle [X; 0] of the rank r + 1 problem along the certificate's negative-curvature direction; the next engine starts
-there.  One rank (world = 1) only: every agent lives in this process."""
+there.  With reduce_tol the certified solution is then truncated to its numerical rank (Graph.rank_reduce) and
+certified again there.  One rank (world = 1) only: every agent lives in this process."""
 from __future__ import annotations
 
 import numpy as np
@@ -16,7 +17,7 @@ class StaircaseError(RuntimeError):
 
 
 def solve(graph: "H.Graph", agent_of_pose, agent_rank, X0, r0, params: "H.RbcdParams | None" = None, r_max=8,
-          eta=1e-6, grad_tol=1e-6, max_steps=10000, cert=None, escape=None):
+          eta=1e-6, grad_tol=1e-6, max_steps=10000, cert=None, escape=None, reduce_tol=None):
     """Solve the pose graph from X0 (r0 x (d+1) n matrix, or its flat column-major buffer), raising the rank until
     the certificate holds.
 
@@ -27,7 +28,14 @@ def solve(graph: "H.Graph", agent_of_pose, agent_rank, X0, r0, params: "H.RbcdPa
 
     Returns (X flat r x (d+1) n column-major, r, levels) with one dict(r, steps, f, gradnorm, lambda_min, alpha,
     trials) per level (alpha = trials = 0 on the last).  Raises StaircaseError when r_max is reached uncertified or an
-    escape is not accepted.  Single rank only (world = 1): agent_rank must be all zero."""
+    escape is not accepted.  Single rank only (world = 1): agent_rank must be all zero.
+
+    reduce_tol (None: nothing more happens): after certification at rank r, Graph.rank_reduce(X, r, reduce_tol)
+    truncates X to its numerical rank k; when k < r an engine at rank k runs from the reduced X (0 or more steps, until
+    grad_tol or max_steps) and Graph.certify decides at rank k.  The rank-k X is returned when it certifies
+    (lambda_min >= -eta), the certified rank-r X otherwise; either way levels gains one entry for rank k that also
+    carries reduced_from = r, dropped (the Gram eigenvalues cut off), w (the Gram's spectrum) and certified.  When
+    the numerical rank is r itself nothing is added and the return is that of reduce_tol=None."""
     ar = np.asarray(agent_rank, dtype=np.int32)
     if np.any(ar != 0):
         raise StaircaseError("staircase.solve runs on one rank: agent_rank must be all zero")
@@ -39,7 +47,9 @@ def solve(graph: "H.Graph", agent_of_pose, agent_rank, X0, r0, params: "H.RbcdPa
     if X.size != r0 * bn:
         raise StaircaseError("X0 has the wrong size for r0")
     r, levels = int(r0), []
-    while True:
+
+    def run_level(r, X):
+        """One engine at rank r from X to a critical point: (X, steps, f, gradnorm)."""
         p = H.RbcdParams()
         for k, _ in H.RbcdParams._fields_:
             setattr(p, k, getattr(base, k))
@@ -59,12 +69,15 @@ def solve(graph: "H.Graph", agent_of_pose, agent_rank, X0, r0, params: "H.RbcdPa
             e.get_X_into(X)
         finally:
             e.close()
+        return X, steps, f, float(np.sqrt(gsq.sum())), p
+
+    while True:
+        X, steps, f, gradnorm, p = run_level(r, X)
         c = graph.certify(X, r, want_vector=True, **cert)
         lam = c["lambda_min"]
-        levels.append(dict(r=r, steps=steps, f=f, gradnorm=float(np.sqrt(gsq.sum())), lambda_min=lam, alpha=0.0,
-                           trials=0))
+        levels.append(dict(r=r, steps=steps, f=f, gradnorm=gradnorm, lambda_min=lam, alpha=0.0, trials=0))
         if lam >= -eta:
-            return X, r, levels
+            break
         if r >= r_max:
             raise StaircaseError(f"rank {r} reached uncertified: lambda_min = {lam:.3e}")
         ep = H.escape_params(min_gradnorm=p.tolerance)
@@ -75,3 +88,13 @@ def solve(graph: "H.Graph", agent_of_pose, agent_rank, X0, r0, params: "H.RbcdPa
         if not info["accepted"]:
             raise StaircaseError(f"escape from rank {r} not accepted: {info}")
         r += 1
+    if reduce_tol is None:
+        return X, r, levels
+    k, Xk, info = graph.rank_reduce(X, r, reduce_tol)
+    if k == r:
+        return X, r, levels
+    Xk, steps, f, gradnorm, _ = run_level(k, Xk)
+    lam = graph.certify(Xk, k, **cert)["lambda_min"]
+    levels.append(dict(r=k, steps=steps, f=f, gradnorm=gradnorm, lambda_min=lam, alpha=0.0, trials=0, reduced_from=r,
+                       dropped=info["dropped"], w=info["w"], certified=bool(lam >= -eta)))
+    return (Xk, k, levels) if lam >= -eta else (X, r, levels)

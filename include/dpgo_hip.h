@@ -327,6 +327,40 @@ void dpgo_hip_default_escape_params(dpgo_escape_params* p);
 int dpgo_hip_escape(dpgo_hip_problem h_next, const double* X, const double* v, double lambda_min,
                     const dpgo_escape_params* params, double* X_out, dpgo_escape_info* info);
 
+/* ---- rank reduction (SE-Sync's last step: truncate a solution to its numerical rank; not in the reference:
+ * pinned against a numpy / long double restatement) ----------------------------------------------------
+ * The way down the staircase.  With X r x (d+1) n, pose j = [Y_j | p_j]:
+ * dpgo_hip_gram: C (r x r, column-major, full symmetric) = sum_j Y_j Y_j^T over the rotation columns only (tr C =
+ * d n on the manifold; at a critical point of a connected graph the translations lie in span(Y) up to the
+ * translation gauge, so no centring is needed).  One streaming kernel that leaves one partial per 128 poses and one
+ * finishing kernel that sums them in a fixed order, no atomics: C is a function of (X, n) alone, bitwise
+ * repeatable, and bitwise the same for any alignment of X.  DPGO_HIP_EINVAL for an unsupported (r, d), n <= 0, or
+ * null X or C. */
+int dpgo_hip_gram(int r, int d, int n, const double* X, double* C);
+/* doubles of the work buffer dpgo_hip_gram_dev needs for (r, d, n): the block partials (0 for bad arguments) */
+long long dpgo_hip_gram_work_doubles(int r, int d, long long n);
+/* the same on device pointers, queued on `stream` (hipStream_t or NULL), no synchronisation; C_dev (r r doubles)
+ * and work_dev (dpgo_hip_gram_work_doubles) must not overlap X_dev or each other */
+int dpgo_hip_gram_dev(int r, int d, long long n, const double* X_dev, double* C_dev, double* work_dev, void* stream);
+/* Eigenpairs of the symmetric r x r matrix C (column-major, r <= 8; its symmetric part is taken) by cyclic Jacobi:
+ * w[r] descending, U (r x r, column-major) the eigenvectors in that order, each column signed so that its
+ * largest-magnitude entry (the first of equals) is positive.  The numerical rank at tolerance tol is
+ * k = max(d, #{i : w_i > tol w_1}); truncating to it drops sum_j |(I - W W^T) Y_j|_F^2 = sum_{i > k} w_i,
+ * W = U[:, :k].  Host only, no device needed.  DPGO_HIP_EINVAL for r outside [1, 8], a null pointer or a
+ * non-finite entry. */
+int dpgo_hip_gram_eig(int r, const double* C, double* w, double* U);
+/* X_out (k x (d+1) n) = the truncation of X to rank k along W (r x k, column-major, host memory: the leading k
+ * columns of dpgo_hip_gram_eig's U), per pose [polar(W^T Y_j) | W^T p_j] with the polar factor of
+ * dpgo_hip_project_polar.  If X has exact rank k, W^T Y_j is already on St(d, k), X_out^T X_out = X^T X and f is
+ * unchanged; at k = d the result lies in O(d) per pose (dpgo_hip_round_se at r = d then handles the determinant;
+ * this pass does not).  A pose whose W^T Y_j is exactly rank-deficient gets a finite, non-orthonormal block (the
+ * Jacobi path leaves a zero singular direction zero).  One streaming kernel.  DPGO_HIP_EINVAL for an unsupported
+ * (r, d) or (k, d), k < d or k >= r, n <= 0, null X, W or X_out, or X_out overlapping X. */
+int dpgo_hip_rank_reduce(int r, int d, int n, const double* X, int k, const double* W, double* X_out);
+/* the same on device pointers (W: host), queued on `stream` (hipStream_t or NULL), no synchronisation */
+int dpgo_hip_rank_reduce_dev(int r, int d, long long n, const double* X_dev, int k, const double* W,
+                             double* X_out_dev, void* stream);
+
 /* ---- measurement helpers ----------------------------------------------------------------*/
 /* Select a compiled kernel variant / host sequence for A/B timing (process-wide; every setting gives
  * results within the documented bars, most bitwise the default's).  key 0: BSR X.Q SpMM

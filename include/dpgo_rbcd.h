@@ -146,6 +146,22 @@ int dpgo_graph_certify_ex(dpgo_graph g, int r, const double* X, int max_iters, i
  * r = 8, r < d, lambda_min >= 0 or a zero direction. */
 int dpgo_graph_escape(dpgo_graph g, int r, const double* X, const double* eigvec_or_v, int vec_rows,
                       double lambda_min, const dpgo_escape_params* params, double* X_out, dpgo_escape_info* info);
+/* The way down again, next to dpgo_graph_escape: truncate X (r x (d+1) n, column-major) to its numerical rank.  X is
+ * uploaded once; dpgo_hip_gram_dev, dpgo_hip_gram_eig on the r x r Gram, *k = max(d, #{i : w_i > tol w_1}), then
+ * dpgo_hip_rank_reduce_dev along the leading k eigenvectors into X_out (k x (d+1) n, column-major; the caller
+ * provides room for r x (d+1) n).  info: the Gram's eigenvalues (w[r..8) = NaN), dropped = sum_{i > k} w_i, and f of
+ * X and of X_out through the central unit-weight edge-stream handles of rank r and k, as dpgo_graph_escape gets
+ * its f.  When k = r nothing is truncated: X_out = X, dropped = 0, f_after = f_before, DPGO_HIP_OK.  X_out then
+ * starts a solver at rank k (dpgo_rbcd_set_X of an engine created with params.r = k).  DPGO_HIP_EINVAL for an
+ * unsupported r, tol outside [0, 1), or a null argument. */
+typedef struct {
+  double w[8];      /* eigenvalues of sum_j Y_j Y_j^T, descending */
+  double dropped;   /* sum_{i > k} w_i = sum_j |(I - W W^T) Y_j|_F^2 */
+  double f_before;  /* f(X) at rank r */
+  double f_after;   /* f(X_out) at rank k */
+} dpgo_rank_info;
+int dpgo_graph_rank_reduce(dpgo_graph g, int r, const double* X, double tol, int* k, double* X_out,
+                           dpgo_rank_info* info);
 int dpgo_graph_grid_partition(dpgo_graph g, int agents_per_axis, int* agent_of_pose);
 
 /* ---- RBCD engine ----------------------------------------------------------------------------*/
@@ -226,6 +242,19 @@ int dpgo_rbcd_get_anchor(dpgo_rbcd e, int pose, double* anchor, int* owned);
  * of a global d x (d+1) n column-major host array (other poses untouched, as get_X).  Only the rounded
  * poses cross to the host.  Synchronises. */
 int dpgo_rbcd_get_trajectory(dpgo_rbcd e, const double* anchor, double* T_global);
+/* ---- rank reduction on the engine's X (dpgo_hip_gram / dpgo_hip_rank_reduce, include/dpgo_hip.h) ------
+ * This rank's partial Gram C (r x r, column-major) = sum over its owned poses of Y_j Y_j^T: the owned buffer is
+ * contiguous, so one dpgo_hip_gram_dev on the engine's stream, and 8 r^2 bytes cross to the host.  Synchronises.  With
+ * several ranks the caller sums the partials (as it broadcasts the anchor): that sum is a valid Gram within the
+ * rounding bound but not bitwise the one-rank value, whose partials cover other spans.  A rank without poses
+ * writes zeros. */
+int dpgo_rbcd_gram(dpgo_rbcd e, double* C);
+/* The engine's X truncated to rank k along W (r x k, column-major, host: the leading eigenvectors of the summed
+ * Gram, dpgo_hip_gram_eig), by dpgo_hip_rank_reduce_dev on the engine's stream, written at the owned poses of a
+ * global k x (d+1) n column-major host array (other poses untouched, as get_X).  Only k (d+1) doubles per pose
+ * cross to the host.  Synchronises.  The merged array starts an engine of rank k (dpgo_rbcd_set_X).
+ * DPGO_HIP_EINVAL for k < d or k >= r. */
+int dpgo_rbcd_get_X_reduced(dpgo_rbcd e, int k, const double* W, double* Xk_global);
 /* current weight of every measurement this rank is responsible for, at its index in the graph's
  * edge order (w[m]; entries of other ranks' edges untouched).  Responsible = dpgo_rbcd_weight_owner's agent
  * lives on this rank; odometry (owner -1) is written by the rank of its agent, always 1.  With
