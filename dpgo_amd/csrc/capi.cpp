@@ -1,9 +1,7 @@
 // C-ABI implementation of libdpgo_hip.so (see include/dpgo_hip.h).
 //
-// Host side of the on-device RTR / tCG state machine.  All vector arithmetic and all scalar
-// recurrences run on the GPU (kernels.hip); the host only sequences launches and, once per RTR
-// Run, reads the per-agent "still running" flags to drive QuadraticOptimizer::trustRegion's
-// radius-shrink retry loop (src/QuadraticOptimizer.cpp:92-110).
+// The entry points, the Q / G upload, certification, and the launch helpers they share with the optimiser
+// driver (optimize.cpp: the host side of the on-device RTR / tCG state machine).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -509,11 +507,13 @@ int problem_ready(dpgo_hip_problem h) { return ready(h); }
 int ensure_work_public(dpgo_hip_problem h) { return ensure_work(h); }
 }  // namespace dpgo
 
-namespace {
+// ---- the launch helpers the optimiser driver (optimize.cpp) shares with the entry points below; declared, with
+// their default arguments, in problem_internal.h
+namespace dpgo {
 
 dpgo::FinalizeArgs make_fin(dpgo_hip_problem h, int op, const double* pa, int nqa, const double* pb, int nqb,
-                            const dpgo::OptScalars* opt = nullptr, const int* enabled = nullptr, int pub_kind = 0,
-                            int pub_tag = 0, int agent_filter = 0) {
+                            const dpgo::OptScalars* opt, const int* enabled, int pub_kind, int pub_tag,
+                            int agent_filter) {
   dpgo::FinalizeArgs f;
   std::memset(&f, 0, sizeof(f));
   f.agent_filter = agent_filter;
@@ -541,8 +541,7 @@ dpgo::FinalizeArgs make_fin(dpgo_hip_problem h, int op, const double* pa, int nq
 }
 
 int finalize(dpgo_hip_problem h, int op, const double* pa, int nqa, const double* pb, int nqb,
-             const dpgo::OptScalars* opt = nullptr, const int* enabled = nullptr, int pub_kind = 0,
-             int pub_tag = 0, int agent_filter = 0) {
+             const dpgo::OptScalars* opt, const int* enabled, int pub_kind, int pub_tag, int agent_filter) {
   const dpgo::FinalizeArgs f = make_fin(h, op, pa, nqa, pb, nqb, opt, enabled, pub_kind, pub_tag, agent_filter);
   HIP_TRY(dpgo::launch_finalize(f, h->K, h->stream));
   return DPGO_HIP_OK;
@@ -575,7 +574,7 @@ int download_sums(dpgo_hip_problem h) {
 // launch lookahead the next iteration's status may overwrite this one before the host looks; a
 // later status is at least as recent, so it answers the question too).  Returns whether any
 // agent's flag is set.  Falls back to a stream synchronisation after 20 s (never expected).
-int wait_published(dpgo_hip_problem h, int tag, bool* any, bool* any_cg = nullptr, bool* any_never = nullptr) {
+int wait_published(dpgo_hip_problem h, int tag, bool* any, bool* any_cg, bool* any_never) {
   const auto t0 = std::chrono::steady_clock::now();
   // DPGO_VERBOSE_WAIT=<ms>: report every wait longer than that (host-side view of GPU idle gaps)
   static const double verbose_ms = std::getenv("DPGO_VERBOSE_WAIT") ? std::atof(std::getenv("DPGO_VERBOSE_WAIT")) : -1.0;
@@ -627,15 +626,18 @@ int download_state(dpgo_hip_problem h) {
 
 // EVAL sweep at X: g = P_X(XQ+G), S, per-agent f and |g|^2 partials into pa.  mode MODE_F: f only;
 // MODE_EVAL_TCG: also the tCG start delta = -Prec(g) and the <z, g> partial.
-int eval_at(dpgo_hip_problem h, const double* X, double* gout, double* Sout, double* part, int flag,
-            int mode = dpgo::MODE_EVAL, double* delta = nullptr, int pmode = dpgo::PRECON_NONE,
-            const dpgo::FinalizeArgs* fin = nullptr) {
+int eval_at(dpgo_hip_problem h, const double* X, double* gout, double* Sout, double* part, int flag, int mode,
+            double* delta, int pmode, const dpgo::FinalizeArgs* fin) {
   auto c = make_ctx(h, flag, part);
   const dpgo::SpmmArgs a{X, h->gidx.p, h->gblk.p, X, nullptr, gout, Sout, h->minv.p, delta, pmode};
   if (fin != nullptr) return spmm_then_finalize(h, mode, c, a, *fin);
   DPGO_TRY(dpgo::spmm_launch(h, mode, c, a));
   return DPGO_HIP_OK;
 }
+
+}  // namespace dpgo
+
+namespace {
 
 struct DevScratch {
   DevBuf<double> a, b, c;
@@ -649,27 +651,6 @@ int download(double* dst, const double* src, size_t n, hipStream_t s) {
   HIP_TRY(hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   return DPGO_HIP_OK;
-}
-
-void fill_result(const AgentState& s, bool single, bool enabled, dpgo_opt_result* out) {
-  std::memset(out, 0, sizeof(*out));
-  out->success = enabled ? 1 : 0;
-  out->fInit = s.f_init;
-  out->gradNormInit = s.ngf_init;
-  if (single) {
-    const bool moved = s.runs > 0 && s.accepted && !s.gave_up;
-    out->fOpt = moved ? s.f2 : s.f_init;
-    out->gradNormOpt = moved ? s.ngf2 : s.ngf_init;
-  } else {
-    out->fOpt = s.f1;
-    out->gradNormOpt = s.ngf;
-  }
-  out->relativeChange = s.rel_change;
-  out->tCGStatus = s.tcg_status;
-  out->runs = s.runs;
-  out->outer_iters = s.outer_iters;
-  out->inner_iters = s.tcg_iters;
-  out->gave_up = s.gave_up;
 }
 
 }  // namespace
@@ -1123,610 +1104,6 @@ int dpgo_hip_optimize_dev(dpgo_hip_problem h, const dpgo_opt_params* params, con
 }
 
 }  // extern "C"
-
-namespace {
-// PGOAgent status pass (src/PGOAgent.cpp:700-716): |X_out - XPrev|^2 per agent, then OP_STATUS.
-// pa already holds |X_out - st->ref|^2 when `have_partials` (the final select compared against ref).
-// `partials`: |X_out - st.ref|^2 per tile already there (nullptr: computed here into pa)
-int status_pass(dpgo_hip_problem h, const double* X_out, const dpgo::StatusArgs& st, const dpgo::OptScalars& o0,
-                const double* partials) {
-  if (!partials) {
-    auto c = make_ctx(h, dpgo::FLAG_NONE, h->pa.p);
-    HIP_TRY(dpgo::launch_sqdiff(h->r, h->b, c, X_out, st.ref));
-    partials = h->pa.p;
-  }
-  dpgo::OptScalars o = o0;
-  o.rel_tol = st.rel_tol;
-  o.min_ratio = st.min_ratio;
-  dpgo::FinalizeArgs f = make_fin(h, dpgo::OP_STATUS, partials, 1, nullptr, 0, &o);
-  f.conv_ratio = st.conv_ratio;
-  HIP_TRY(dpgo::launch_finalize(f, h->K, h->stream));
-  return DPGO_HIP_OK;
-}
-}  // namespace
-
-// --------------------------------------------------------------------------- optimisation
-int dpgo::optimize_dev_status(dpgo_hip_problem h, const dpgo_opt_params* params, const double* X_in, double* X_out,
-                              const int* agent_enabled_host, dpgo_opt_result* results, const StatusArgs* st) {
-  DPGO_TRY(ready(h));
-  dpgo_opt_params P;
-  if (params)
-    P = *params;
-  else
-    dpgo_hip_default_params(&P);
-  if (P.tr_iterations < 1 || P.tr_max_inner < 0) return fail(DPGO_HIP_EINVAL, "bad optimizer parameters");
-  DPGO_TRY(ensure_work(h));
-  const auto t0 = std::chrono::high_resolution_clock::now();
-  const int r = h->r, b = h->b, K = h->K;
-  const bool exact = P.precon == DPGO_PRECON_EXACT;
-  if (exact) DPGO_TRY(sync_chol(h));
-  // the exact solve runs as its own stages; the fused tCG kernels then see the identity
-  const int pmode = P.precon == DPGO_PRECON_BLOCK_JACOBI ? dpgo::PRECON_BLOCK_JACOBI : dpgo::PRECON_NONE;
-  std::vector<int> en(K, 1);
-  if (agent_enabled_host)
-    for (int a = 0; a < K; ++a) en[a] = agent_enabled_host[a] != 0;
-  // (a pageable H2D copy would synchronise the stream: only copy when a mask is given)
-  if (agent_enabled_host)
-    HIP_TRY(hipMemcpyAsync(h->enabled.p, en.data(), sizeof(int) * K, hipMemcpyHostToDevice, h->stream));
-  // without a mask every agent is enabled: k_finalize reads no mask (no fill launch)
-  const int* en_dev = agent_enabled_host ? h->enabled.p : nullptr;
-
-  const bool single = P.algorithm == DPGO_ALG_RTR && P.tr_iterations == 1;
-  // x1 only moves in a multi-iteration Run; a single Run (the RBCD setting) reads X_in in place.
-  double* x1 = h->x1.p;
-  if (single || P.algorithm == DPGO_ALG_RGD) {
-    x1 = const_cast<double*>(X_in);
-  } else {
-    HIP_TRY(hipMemcpyAsync(h->x1.p, X_in, h->vec_bytes(), hipMemcpyDeviceToDevice, h->stream));
-  }
-  dpgo::OptScalars o;
-  std::memset(&o, 0, sizeof(o));
-  o.tol = P.tr_tolerance;
-  o.Delta0 = P.tr_initial_radius;
-  o.Delta_max = single ? P.tr_initial_radius : 5.0 * P.tr_initial_radius;
-  o.theta = 1.0;
-  o.kappa = 0.1;
-  o.min_inner = 0;
-  o.max_iter = P.tr_iterations;
-  o.single_run = single ? 1 : 0;
-  // f(x1), grad(x1), S(x1)  (QuadraticOptimizer::optimize :36-37, SolversTR start); for RTR the
-  // first tCG start (delta = -Prec(grad), <z, grad>) is fused into the same pass
-  const bool fused_tcg = P.algorithm == DPGO_ALG_RTR && P.tr_max_inner > 0 && !exact;
-  // grad(x1) itself is only read by a CG step (r = grad + alpha Hdelta), a retry Run or the explicit
-  // <g, eta>: when the previous call's first step stopped every agent (single Run), it is not stored
-  // and is recomputed, by the same MODE_EVAL_TCG pass (bitwise the same g), if it is needed.  This
-  // only chooses between storing and recomputing identical values: no result depends on it, so an
-  // agent's arithmetic does not depend on which other agents share its handle.
-  // (a first step forced to the full pass reads grad(x1) in that pass already: the merged HESS_QF_M's r_0)
-  bool g_valid = !(fused_tcg && single && h->predict_boundary && P.tr_max_inner > 0 &&
-                   h->tuning[dpgo::TUNE_FIRST_STEP] != 2);
-  if (fused_tcg) {
-    const dpgo::FinalizeArgs fin = make_fin(h, dpgo::OP_EVAL_TCG_INIT, h->pa.p, 3, nullptr, 0, &o, en_dev);
-    DPGO_TRY(eval_at(h, x1, g_valid ? h->g.p : nullptr, h->S.p, h->pa.p, dpgo::FLAG_NONE, dpgo::MODE_EVAL_TCG,
-                     h->delta.p, pmode, &fin));
-  } else {
-    DPGO_TRY(eval_at(h, x1, h->g.p, h->S.p, h->pa.p, dpgo::FLAG_NONE));
-    DPGO_TRY(finalize(h, dpgo::OP_EVAL_INIT, h->pa.p, 2, nullptr, 0, &o, en_dev));
-  }
-
-  if (P.algorithm == DPGO_ALG_RGD) {
-    // one fixed-step Riemannian gradient step (QuadraticOptimizer::gradientDescent :124-149)
-    auto cr = make_ctx(h, dpgo::FLAG_NONE, h->pb.p);
-    HIP_TRY(dpgo::launch_retract(r, b, cr, x1, h->g.p, -P.rgd_stepsize, h->x2.p, nullptr, nullptr));
-    HIP_TRY(hipMemcpyAsync(h->use_a.p, en.data(), sizeof(int) * K, hipMemcpyHostToDevice, h->stream));
-    // X_in may alias X_out (in-place update): the candidate stays in x2 until the select
-    auto cs = make_ctx(h, dpgo::FLAG_NONE, h->pa.p);
-    const bool want = results != nullptr || P.verbose;
-    // one pass: X_out = x2 and the partials |X_out - X_in|^2 (pa).  When the status reference is X_in
-    // (PGOAgent's XPrev), those partials ARE the status's: an in-place update (X_out == X_in, the engine's)
-    // has overwritten X_in by now, so they must not be recomputed from memory.
-    HIP_TRY(dpgo::launch_select(r, b, cs, h->x2.p, x1, h->use_a.p, x1, X_out));
-    if (want) DPGO_TRY(finalize(h, dpgo::OP_REL_CHANGE, h->pa.p, 1, nullptr, 0));
-    if (st) DPGO_TRY(status_pass(h, X_out, *st, o, st->ref == X_in ? h->pa.p : nullptr));
-    if (!want) return DPGO_HIP_OK;
-    DPGO_TRY(eval_at(h, X_out, h->g2.p, h->S2.p, h->pb.p, dpgo::FLAG_NONE));
-    DPGO_TRY(finalize(h, dpgo::OP_SUM, h->pb.p, 2, nullptr, 0));
-    DPGO_TRY(download_sums(h));
-    DPGO_TRY(download_state(h));
-    const double ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
-    if (results) {
-      for (int a = 0; a < K; ++a) {
-        const AgentState& s = h->h_state[a];
-        dpgo_opt_result* out = &results[a];
-        std::memset(out, 0, sizeof(*out));
-        out->success = en[a];
-        out->fInit = s.f_init;
-        out->gradNormInit = s.ngf_init;
-        out->fOpt = en[a] ? h->h_sums[a * 4] : s.f_init;
-        out->gradNormOpt = en[a] ? std::sqrt(h->h_sums[a * 4 + 1]) : s.ngf_init;
-        out->relativeChange = s.rel_change;
-        out->elapsedMs = std::floor(ms);
-        out->tCGStatus = -1;
-      }
-    }
-    return DPGO_HIP_OK;
-  }
-
-  if (P.tr_max_inner == 0) HIP_TRY(hipMemsetAsync(h->eta.p, 0, h->vec_bytes(), h->stream));
-  // Host control without stream synchronisation: k_finalize publishes each agent's tCG / Run flag
-  // to host-mapped memory; the host keeps one tCG iteration of launches queued ahead of the flag
-  // it is waiting for, so the GPU never drains (agents that finished skip their tiles).
-  const int max_rounds = single ? 12 : P.tr_iterations;
-  // Statistics nobody asked for are not computed: without results / verbose, the x2 evaluation of
-  // a single Run needs f(x2) only (gradNormOpt is only printed, src/PGOAgent.cpp:1155-1161), and an
-  // accepted candidate is retracted straight into X_out (only agents that did not move copy X_in).
-  const bool stats = results != nullptr || P.verbose;
-  const bool direct = single && !stats && X_out != X_in;
-  double* x2 = direct ? X_out : h->x2.p;
-  bool status_done = false;  // the status was folded into the last rho test for every agent
-  for (int round = 0; round < max_rounds; ++round) {
-    // ---- truncated CG (A.4)
-    if (round > 0 || !fused_tcg) {
-      if (!g_valid) {  // a retry Run restarts tCG from grad(x1), which EVAL_TCG did not store
-        DPGO_TRY(eval_at(h, x1, h->g.p, h->S.p, h->pa.p, dpgo::FLAG_RUN, dpgo::MODE_EVAL_TCG, h->delta.p, pmode));
-        g_valid = true;
-      }
-      if (exact) {  // delta = -P_X(g P^-1), partials <z, g>, |g|^2
-        DPGO_TRY(exact_precond(h, h->g.p, nullptr, h->delta.p, x1, h->g.p, h->pa.p, dpgo::FLAG_RUN));
-      } else {
-        auto ci = make_ctx(h, dpgo::FLAG_RUN, h->pa.p);
-        HIP_TRY(dpgo::launch_tcg_init(r, b, ci, x1, h->minv.p, pmode, h->g.p, h->delta.p));
-      }
-      DPGO_TRY(finalize(h, dpgo::OP_TCG_INIT, h->pa.p, 2, nullptr, 0, &o));
-    }
-    std::vector<int> tags, step_tags;
-    // Consumer-side finalize (TUNE_FUSE_TCG): the step test's scalar logic runs in the update kernel's
-    // prologue and the stopping test's in the direction update's, three launches per tCG iteration.
-    const bool fuse_tcg = h->tuning[dpgo::TUNE_FUSE_TCG] > 0 && !exact;
-    // iteration j's step test: Hdelta = Hess[delta] and d_Hd = <delta, Hdelta> (MODE_HESS); for the
-    // first step d_Hd by the each-edge-once formula, alone (MODE_QF) or with Hdelta stored (MODE_HESS_QF)
-    auto launch_step = [&](int mode) -> int {
-      auto ch = make_ctx(h, dpgo::FLAG_TCG, h->pa.p);
-      // the step test publishes too: when it already stopped every agent (a boundary or
-      // negative-curvature step, the common RBCD case) the host launches no further iteration
-      const int stag = next_tag(h);
-      step_tags.push_back(stag);
-      const bool qf = mode == dpgo::MODE_QF;
-      const dpgo::SpmmArgs sa{h->delta.p, nullptr, nullptr, x1, h->S.p, qf ? nullptr : h->Hdelta.p, nullptr,
-                              nullptr, nullptr, dpgo::PRECON_NONE};
-      if (fuse_tcg && mode == dpgo::MODE_HESS) return dpgo::spmm_launch(h, mode, ch, sa);  // decided by the update
-      dpgo::OptScalars os = o;
-      os.first_full = mode == dpgo::MODE_HESS_QF ? 1 : 0;
-      return spmm_then_finalize(h, mode, ch, sa,
-                                make_fin(h, dpgo::OP_TCG_STEP, h->pa.p, 1, nullptr, 0, &os, nullptr, 1, stag));
-    };
-    // the first step after a QF step test was decided by the QF pass's finalize
-    auto launch_rest = [&](int j, bool step_decided) -> int {
-      auto cu = make_ctx(h, dpgo::FLAG_TCG_MODE, h->pb.p);
-      const bool fs = fuse_tcg && !step_decided;
-      const dpgo::FinalizeArgs fstep =
-          make_fin(h, dpgo::OP_TCG_STEP, h->pa.p, 1, nullptr, 0, &o, nullptr, 1, step_tags[j]);
-      HIP_TRY(dpgo::launch_tcg_update(r, b, cu, x1, h->minv.p, pmode, h->delta.p, h->Hdelta.p, h->eta.p,
-                                      j == 0 ? h->g.p : h->rv.p, h->rv.p, h->z.p, j == 0 ? 1 : 0,
-                                      fs ? &fstep : nullptr, h->arrive.p));
-      if (exact)  // z = Prec(r) with the factor; replaces the identity z and its partials
-        DPGO_TRY(exact_precond(h, h->rv.p, h->z.p, nullptr, x1, h->rv.p, h->pb.p, dpgo::FLAG_TCG_MODE));
-      const int tag = next_tag(h);
-      tags.push_back(tag);
-      const dpgo::FinalizeArgs fcheck = make_fin(h, dpgo::OP_TCG_CHECK, h->pb.p, 3, nullptr, 0, &o, nullptr, 1, tag);
-      const bool dir = j + 1 < P.tr_max_inner;  // the last direction update is never used
-      if (!(fuse_tcg && dir)) HIP_TRY(dpgo::launch_finalize(fcheck, h->K, h->stream));
-      if (dir) {
-        auto cd = make_ctx(h, dpgo::FLAG_TCG, nullptr);
-        HIP_TRY(dpgo::launch_tcg_dir(r, b, cd, h->z.p, h->delta.p, fuse_tcg ? &fcheck : nullptr, h->arrive.p));
-      }
-      return DPGO_HIP_OK;
-    };
-    // First step: only d_Hd is evaluated (MODE_QF: each edge once, no Hess[delta] vector).  A
-    // boundary / negative-curvature exit needs nothing more (eta = tau delta stays implicit, <eta, Heta>
-    // = tau^2 d_Hd); agents that take a CG step get Hess[delta] from a HESS pass over their tiles only.
-    // Always the same formula for the first d_Hd, so an agent's result does not depend on the batch.
-    const bool qf0 = !exact && P.tr_max_inner > 0;
-    // When the previous call took CG steps the first step test is the full pass (MODE_HESS_QF): same
-    // d_Hd, and Hess[delta] is there for the agents that continue (no second pass over them).
-    const int first_kind = h->tuning[dpgo::TUNE_FIRST_STEP];
-    const bool full0 = qf0 && (first_kind == 2 || (first_kind == 0 && !h->predict_boundary));
-    // Single Run, first steps predicted on the boundary: the candidate, f(x2) and the rho test of the
-    // agents whose first step already ended tCG are queued right behind the step test, before the host
-    // learns whether any agent continues (those are retracted, evaluated and tested after their tCG:
-    // the *_EXPL launches below).
-    const bool spec = qf0 && single && !full0;
-    // PGOAgent status folded into the retraction + rho test of a single Run (no k_sqdiff / OP_STATUS pass);
-    // agents that never ran this call (|grad| < tol) are the separate pass's, run only when some did
-    const bool status_fold = st != nullptr && single && h->tuning[dpgo::TUNE_STATUS_PASS] == 0;
-    // Merged tCG iteration (the default with block-Jacobi / no preconditioner): HESS_M, one finalize for
-    // the step test and the stopping test (OP_TCG_STEP_CHECK), then k_tcg_updir -- three launches per
-    // iteration instead of five, no z vector.  The exact preconditioner and TUNE_FUSE_TCG keep the
-    // classic sequence (TUNE_CLASSIC_TCG forces it).
-    const bool merged = qf0 && !fuse_tcg && h->tuning[dpgo::TUNE_CLASSIC_TCG] == 0;
-    // TUNE_TAIL_FUSE: the last iteration's k_tcg_updir (eta += step delta and the <eta_old, Hdelta> partial, nothing
-    // else) is not launched; the retraction that follows applies the step from registers (RetractTail).  Every path
-    // to the last iteration goes through launch_merged / launch_merged_range, which set tail_pending instead of
-    // launching; launch_candidate hands it to the retraction.  Both kernels would read the state the last
-    // OP_TCG_STEP_CHECK / OP_TCG_CHECK_M left: no finalize runs between them.
-    const bool tail_fuse = merged && h->tuning[dpgo::TUNE_TAIL_FUSE] > 0;
-    bool tail_pending = false;  // this Run's last merged iteration was queued without its k_tcg_updir
-    auto launch_merged = [&](int j, int mode, int flag, int op, bool publish = true) -> int {
-      auto ch = make_ctx(h, flag, h->pa.p);
-      const int tag = publish ? next_tag(h) : 0;
-      tags.push_back(tag);
-      dpgo::SpmmArgs sa{h->delta.p, nullptr, nullptr, x1, h->S.p, h->Hdelta.p, nullptr, h->minv.p, nullptr, pmode};
-      sa.rvec = j == 0 ? h->g.p : h->rv.p;
-      // |r_j|^2 and <z_j, r_j>: from the previous k_tcg_updir's partials (peh), formed by the SpMM itself on
-      // the first iteration (r_0 = grad)
-      const bool rz_pc = j > 0;
-      sa.rz_own = rz_pc ? 0 : 1;
-      dpgo::OptScalars os = o;
-      os.first_full = mode == dpgo::MODE_HESS_QF_M ? 1 : 0;
-      dpgo::FinalizeArgs fin = make_fin(h, op, h->pa.p, 7, nullptr, 0, &os, nullptr, publish ? 1 : 0, tag);
-      fin.pc = h->peh.p;
-      fin.nq_c = 1;
-      fin.dd_mask = dpgo::merged_dd_mask(h->fmt, h->tuning);  // which merged partials are double-double
-      fin.rz_pc = rz_pc ? 1 : 0;
-      DPGO_TRY(spmm_then_finalize(h, mode, ch, sa, fin));
-      if (tail_fuse && j + 1 == P.tr_max_inner) {  // the retraction draws the tile order this launch would have
-        tail_pending = true;
-        return DPGO_HIP_OK;
-      }
-      auto cu = make_ctx(h, dpgo::FLAG_TCG_MODE, h->peh.p);
-      HIP_TRY(dpgo::launch_tcg_updir(r, b, cu, x1, h->minv.p, pmode, h->delta.p, h->Hdelta.p, h->eta.p,
-                                     j == 0 ? h->g.p : h->rv.p, h->rv.p, j == 0 ? 1 : 0,
-                                     j + 1 == P.tr_max_inner ? 1 : 0));
-      return DPGO_HIP_OK;
-    };
-    auto launch_candidate = [&](int run_flag, int filter) -> int {
-      auto cr = make_ctx(h, run_flag, h->pa.p);
-      // a pending last step: its partial goes to peh (the rho test's FinalizeArgs::pc below), the retraction's to pa
-      const dpgo::RetractTail tail{h->delta.p, h->Hdelta.p, h->peh.p, P.tr_max_inner == 1 ? 1 : 0};
-      const bool with_tail = tail_pending && run_flag != dpgo::FLAG_RUN_IMPL;
-      HIP_TRY(dpgo::launch_retract(r, b, cr, x1, h->eta.p, 1.0, x2, h->g.p, nullptr, h->delta.p,
-                                   status_fold ? st->ref : nullptr, with_tail ? &tail : nullptr));
-      if (with_tail) tail_pending = false;
-      // single Run: only f(x2) and |grad(x2)| are consumed (fOpt / gradNormOpt), |grad(x2)| only as a
-      // statistic
-      const int rtag = next_tag(h);
-      dpgo::OptScalars orho = o;
-      orho.tail_fused = with_tail ? 1 : 0;
-      if (status_fold) {
-        orho.status_fold = 1;
-        orho.rel_tol = st->rel_tol;
-        orho.min_ratio = st->min_ratio;
-      }
-      dpgo::FinalizeArgs fin = make_fin(h, dpgo::OP_RHO, h->pa.p, status_fold ? 4 : 2, h->pb.p, 2, &orho, nullptr, 2,
-                                        rtag, filter);
-      if (status_fold) fin.conv_ratio = st->conv_ratio;
-      if (merged) {  // the last k_tcg_updir's <eta_old, Hdelta>, folded before the rho test
-        fin.pc = h->peh.p;
-        fin.nq_c = 1;
-      }
-      if (single)
-        DPGO_TRY(eval_at(h, x2, nullptr, nullptr, h->pb.p, run_flag, stats ? dpgo::MODE_EVAL : dpgo::MODE_F,
-                         nullptr, dpgo::PRECON_NONE, &fin));
-      else
-        DPGO_TRY(eval_at(h, x2, h->g2.p, h->S2.p, h->pb.p, run_flag, dpgo::MODE_EVAL, nullptr, dpgo::PRECON_NONE,
-                         &fin));
-      return rtag;
-    };
-    // The same iteration over agents [a0, a1) only, on `on` (TUNE_SPLIT_STREAMS): tiles, partial slots and
-    // finalize rows of that agent range; every kernel of the iteration reads and writes only those agents'
-    // poses (Q and the tCG vectors are block-diagonal over agents), so the halves are independent and each
-    // agent's arithmetic is the unsplit launch's, bit for bit.
-    // order_h / order_u: the tile orders of the iteration's HESS_M and k_tcg_updir, drawn once per iteration so that
-    // every agent group runs a phase in the same direction (each group's own tiles then alternate launch by launch)
-    auto launch_merged_range = [&](int j, int mode, int flag, int op, int a0, int a1, hipStream_t on, int order_h,
-                                   int order_u) -> int {
-      const int t0 = h->h_agent_tile_off[a0], t1 = h->h_agent_tile_off[a1];
-      if (t1 == t0) return DPGO_HIP_OK;
-      auto sub = [&](double* partials, int order) {
-        dpgo::LaunchCtx c = dpgo::make_ctx_order(h, flag, partials + static_cast<long>(t0) * dpgo::kPartialStride, order);
-        c.tile_agent += t0;
-        c.tile_start += t0;
-        c.tile_count += t0;
-        if (c.tile_meta) c.tile_meta += t0;
-        c.num_tiles = t1 - t0;
-        c.stream = on;
-        return c;
-      };
-      dpgo::SpmmArgs sa{h->delta.p, nullptr, nullptr, x1, h->S.p, h->Hdelta.p, nullptr, h->minv.p, nullptr, pmode};
-      sa.rvec = j == 0 ? h->g.p : h->rv.p;
-      const bool rz_pc = j > 0;
-      sa.rz_own = rz_pc ? 0 : 1;
-      dpgo::OptScalars os = o;
-      os.first_full = mode == dpgo::MODE_HESS_QF_M ? 1 : 0;
-      dpgo::FinalizeArgs fin = make_fin(h, op, h->pa.p, 7, nullptr, 0, &os, nullptr, 0, 0);
-      fin.pc = h->peh.p;
-      fin.nq_c = 1;
-      fin.dd_mask = dpgo::merged_dd_mask(h->fmt, h->tuning);
-      fin.rz_pc = rz_pc ? 1 : 0;
-      fin.agent_tile_off += a0;  // tile offsets stay global: the partial slots are the unsplit ones
-      fin.agent_num_poses += a0;
-      fin.state += a0;
-      fin.out_sums += 4 * a0;
-      if (fin.trace) fin.trace += static_cast<long>(a0) * fin.trace_cap * dpgo::kTraceWidth;
-      DPGO_TRY(dpgo::spmm_launch(h, mode, sub(h->pa.p, order_h), sa));
-      HIP_TRY(dpgo::launch_finalize(fin, a1 - a0, on));
-      if (tail_fuse && j + 1 == P.tr_max_inner) {  // every group's last step waits for the (unsplit) retraction
-        tail_pending = true;
-        return DPGO_HIP_OK;
-      }
-      auto cu = sub(h->peh.p, order_u);
-      cu.flag_kind = dpgo::FLAG_TCG_MODE;
-      HIP_TRY(dpgo::launch_tcg_updir(r, b, cu, x1, h->minv.p, pmode, h->delta.p, h->Hdelta.p, h->eta.p,
-                                     j == 0 ? h->g.p : h->rv.p, h->rv.p, j == 0 ? 1 : 0,
-                                     j + 1 == P.tr_max_inner ? 1 : 0));
-      return DPGO_HIP_OK;
-    };
-    int launched = 0, rtag = 0;
-    bool cg_agents = !qf0;  // some agent may still be in tCG after the first step test
-    // Every iteration queued at once, no status published inside tCG (the CG regime, where tCG runs
-    // to MAXITER or close: agents that stop skip their tiles, an all-stopped iteration costs three
-    // near-empty launches).  Adaptive (default): when the previous call's tCG took CG steps.
-    const int la = h->tuning[dpgo::TUNE_TCG_LOOKAHEAD];
-    const bool all_ahead = merged && single && full0 && la != 1 && (la == 2 || !h->predict_boundary);
-    // TUNE_TCG_BLOCK: the batch's agents in blocks of consecutive agents, each block's iterations queued depth-first
-    // (agent boundaries in tcg_blocks; fewer than two blocks: not applied)
-    std::vector<int> tcg_blocks;
-    if (all_ahead) dpgo::merged_blocks(h, &tcg_blocks);
-    const bool blocked = tcg_blocks.size() > 2;
-    if (round == 0) h->tcg_blocks_last = 0;  // (a call's Runs: the first and its radius-shrink retries)
-    if (blocked) h->tcg_blocks_last = static_cast<int>(tcg_blocks.size()) - 1;
-    const bool split = all_ahead && !blocked && dpgo::merged_split(h);
-    // The classic sequence (the exact preconditioner) queued the same way on request (TUNE_TCG_LOOKAHEAD = 2 only):
-    // every iteration at once, agents that stopped skip their tiles and their supernodes, no status round trip
-    // inside tCG.  Bitwise the one-ahead sequence (test_exact_lookahead_bitwise) but not the default: the dead
-    // iterations cost more than the round trips they save (same-process A/B: C4 17.4 vs 16.7 ms/step, C5 101.8 vs
-    // 100.8, profiles/r03ze_*).
-    const bool classic_ahead = !merged && single && !qf0 && P.tr_max_inner > 0 && la == 2;
-    if (blocked) {
-      // Block b runs its tr_max_inner iterations back to back on stream b % S (0: the launch stream, s:
-      // split_stream[s - 1]), so two touches of a block's lines are one block launch apart instead of one batch
-      // launch and at most S blocks are in flight.  Queued wave by wave (S blocks), a wave's blocks interleaved per
-      // iteration so every stream has work from the first launches on.  One pair of tile orders per wave and
-      // iteration: each block's consecutive launches alternate direction.
-      const int B = static_cast<int>(tcg_blocks.size()) - 1;
-      const int S = std::max(1, std::min({h->tuning[dpgo::TUNE_TCG_BLOCK_STREAMS], 4, B}));
-      static_assert(dpgo_hip_problem_s::kMaxSplit >= 4, "streams of TUNE_TCG_BLOCK_STREAMS");
-      if (S > 1 && !h->split_fork) HIP_TRY(hipEventCreateWithFlags(&h->split_fork, hipEventDisableTiming));
-      for (int s = 0; s + 1 < S; ++s) {
-        if (!h->split_stream[s]) HIP_TRY(hipStreamCreateWithFlags(&h->split_stream[s], hipStreamNonBlocking));
-        if (!h->split_join[s]) HIP_TRY(hipEventCreateWithFlags(&h->split_join[s], hipEventDisableTiming));
-      }
-      auto on = [&](int s) { return s == 0 ? h->stream : h->split_stream[s - 1]; };
-      if (S > 1) {
-        HIP_TRY(hipEventRecord(h->split_fork, h->stream));
-        for (int s = 1; s < S; ++s) HIP_TRY(hipStreamWaitEvent(on(s), h->split_fork, 0));
-      }
-      for (int w = 0; w < B; w += S) {
-        for (int j = 0; j < P.tr_max_inner; ++j) {
-          const int mode = j == 0 ? dpgo::MODE_HESS_QF_M : dpgo::MODE_HESS_M;
-          const int oh = dpgo::tile_order_next(h);
-          const int ou = tail_fuse && j + 1 == P.tr_max_inner ? 0 : dpgo::tile_order_next(h);
-          for (int s = 0; s < S && w + s < B; ++s)
-            DPGO_TRY(launch_merged_range(j, mode, dpgo::FLAG_TCG, dpgo::OP_TCG_STEP_CHECK, tcg_blocks[w + s],
-                                         tcg_blocks[w + s + 1], on(s), oh, ou));
-        }
-      }
-      for (int s = 1; s < S; ++s) {
-        HIP_TRY(hipEventRecord(h->split_join[s - 1], on(s)));
-        HIP_TRY(hipStreamWaitEvent(h->stream, h->split_join[s - 1], 0));
-      }
-      cg_agents = true;
-    } else if (split) {
-      // groups of agents [a_g, a_g+1): two halves (values 1, 2), four groups (3) or one group per agent up to
-      // eight (4); group 0 on the launch stream, group g on split_stream[g - 1]
-      const int sv = h->tuning[dpgo::TUNE_SPLIT_STREAMS];
-      const int G = std::min(K, sv == 3 ? 4 : sv >= 4 ? dpgo_hip_problem_s::kMaxSplit : 2);
-      if (!h->split_fork) HIP_TRY(hipEventCreateWithFlags(&h->split_fork, hipEventDisableTiming));
-      for (int g = 0; g + 1 < G; ++g) {
-        if (!h->split_stream[g]) HIP_TRY(hipStreamCreateWithFlags(&h->split_stream[g], hipStreamNonBlocking));
-        if (!h->split_join[g]) HIP_TRY(hipEventCreateWithFlags(&h->split_join[g], hipEventDisableTiming));
-      }
-      auto on = [&](int g) { return g == 0 ? h->stream : h->split_stream[g - 1]; };
-      auto first = [&](int g) { return static_cast<int>(static_cast<long>(K) * g / G); };
-      // value 2: the second half starts once the first half's first iteration is done, so the two halves run
-      // out of phase (one half's HESS_M beside the other's k_tcg_updir) rather than side by side
-      const bool offset = sv == 2 && G == 2;
-      if (!offset) {
-        HIP_TRY(hipEventRecord(h->split_fork, h->stream));
-        for (int g = 1; g < G; ++g) HIP_TRY(hipStreamWaitEvent(on(g), h->split_fork, 0));
-      }
-      for (int j = 0; j < P.tr_max_inner; ++j) {
-        const int mode = j == 0 ? dpgo::MODE_HESS_QF_M : dpgo::MODE_HESS_M;
-        // (a fused last iteration launches no k_tcg_updir and draws no order for it)
-        const int oh = dpgo::tile_order_next(h);
-        const int ou = tail_fuse && j + 1 == P.tr_max_inner ? 0 : dpgo::tile_order_next(h);
-        DPGO_TRY(launch_merged_range(j, mode, dpgo::FLAG_TCG, dpgo::OP_TCG_STEP_CHECK, first(0), first(1), on(0), oh, ou));
-        if (offset && j == 0) {
-          HIP_TRY(hipEventRecord(h->split_fork, h->stream));
-          HIP_TRY(hipStreamWaitEvent(on(1), h->split_fork, 0));
-        }
-        for (int g = 1; g < G; ++g)
-          DPGO_TRY(launch_merged_range(j, mode, dpgo::FLAG_TCG, dpgo::OP_TCG_STEP_CHECK, first(g), first(g + 1), on(g), oh,
-                                       ou));
-      }
-      for (int g = 1; g < G; ++g) {
-        HIP_TRY(hipEventRecord(h->split_join[g - 1], on(g)));
-        HIP_TRY(hipStreamWaitEvent(h->stream, h->split_join[g - 1], 0));
-      }
-      cg_agents = true;
-    } else if (all_ahead) {
-      for (int j = 0; j < P.tr_max_inner; ++j)
-        DPGO_TRY(launch_merged(j, j == 0 ? dpgo::MODE_HESS_QF_M : dpgo::MODE_HESS_M, dpgo::FLAG_TCG,
-                               dpgo::OP_TCG_STEP_CHECK, false));
-      cg_agents = true;
-    } else if (merged) {
-      // first step: MODE_QF (boundary predicted; CG-step agents then get a HESS_M pass and the stopping
-      // test alone) or the full HESS_QF_M pass; one published status per iteration, one iteration queued
-      // ahead of the status the host waits for
-      if (full0) {
-        DPGO_TRY(launch_merged(0, dpgo::MODE_HESS_QF_M, dpgo::FLAG_TCG, dpgo::OP_TCG_STEP_CHECK));
-      } else {
-        DPGO_TRY(launch_step(dpgo::MODE_QF));
-        if (spec) {
-          rtag = launch_candidate(dpgo::FLAG_RUN_IMPL, 1);
-          if (rtag < 0) return rtag;
-        }
-      }
-      launched = 1;
-      for (int j = 0; j < P.tr_max_inner; ++j) {
-        bool act = false;
-        if (j == 0 && !full0) {
-          DPGO_TRY(wait_published(h, step_tags[0], &act));  // after the QF step test
-          h->predict_boundary = !act;
-          cg_agents = act;
-          if (!act) break;
-          if (!g_valid)  // the CG-step agents' gradient (EVAL_TCG skipped storing it; same pass again)
-            DPGO_TRY(eval_at(h, x1, h->g.p, h->S.p, h->pa.p, dpgo::FLAG_TCG_CG, dpgo::MODE_EVAL_TCG, h->delta.p, pmode));
-          DPGO_TRY(launch_merged(0, dpgo::MODE_HESS_M, dpgo::FLAG_TCG_CG, dpgo::OP_TCG_CHECK_M));
-        }
-        if (launched < P.tr_max_inner) {  // lookahead: iteration j+1 queued while j runs
-          DPGO_TRY(launch_merged(launched, dpgo::MODE_HESS_M, dpgo::FLAG_TCG, dpgo::OP_TCG_STEP_CHECK));
-          ++launched;
-        }
-        DPGO_TRY(wait_published(h, tags[j], &act));  // after iteration j's step and stopping tests
-        if (j == 0 && full0) {
-          h->predict_boundary = !act;
-          cg_agents = act;
-        }
-        if (!act) break;
-      }
-    } else if (P.tr_max_inner > 0) {
-      DPGO_TRY(launch_step(full0 ? dpgo::MODE_HESS_QF : qf0 ? dpgo::MODE_QF : dpgo::MODE_HESS));
-      if (spec) {
-        rtag = launch_candidate(dpgo::FLAG_RUN_IMPL, 1);
-        if (rtag < 0) return rtag;
-      }
-      if (!qf0) DPGO_TRY(launch_rest(0, false));
-      launched = 1;
-      if (classic_ahead) {
-        for (; launched < P.tr_max_inner; ++launched) {
-          DPGO_TRY(launch_step(dpgo::MODE_HESS));
-          DPGO_TRY(launch_rest(launched, false));
-        }
-        cg_agents = true;
-      }
-    }
-    for (int j = 0; !merged && !classic_ahead && j < P.tr_max_inner; ++j) {
-      bool act = false;
-      DPGO_TRY(wait_published(h, step_tags[j], &act));  // after the step test of iteration j
-      if (j == 0) {
-        h->predict_boundary = !act;
-        cg_agents = act;
-      }
-      if (!act) break;
-      if (j == 0 && qf0) {
-        if (!g_valid)  // the CG-step agents' gradient (EVAL_TCG skipped storing it; same pass again)
-          DPGO_TRY(eval_at(h, x1, h->g.p, h->S.p, h->pa.p, dpgo::FLAG_TCG_CG, dpgo::MODE_EVAL_TCG, h->delta.p, pmode));
-        if (!full0) {  // Hess[delta] of the agents taking a CG step (the QF pass did not form it)
-          auto cg = make_ctx(h, dpgo::FLAG_TCG_CG, h->pb.p);
-          DPGO_TRY(dpgo::spmm_launch(h, dpgo::MODE_HESS, cg,
-                                     dpgo::SpmmArgs{h->delta.p, nullptr, nullptr, x1, h->S.p, h->Hdelta.p, nullptr,
-                                                    nullptr, nullptr, dpgo::PRECON_NONE}));
-        }
-        DPGO_TRY(launch_rest(0, true));
-      }
-      if (launched < P.tr_max_inner) {  // lookahead: iteration j+1 queued while j's update runs
-        DPGO_TRY(launch_step(dpgo::MODE_HESS));
-        DPGO_TRY(launch_rest(launched, false));
-        ++launched;
-      }
-      DPGO_TRY(wait_published(h, tags[j], &act));  // after the stopping test of iteration j
-      if (!act) break;
-    }
-    // ---- candidate x2 = R_x1(eta), rho test, radius update
-    if (!spec) {
-      rtag = launch_candidate(dpgo::FLAG_RUN, 0);
-      if (rtag < 0) return rtag;
-    } else if (cg_agents) {
-      rtag = launch_candidate(dpgo::FLAG_RUN_EXPL, 2);
-      if (rtag < 0) return rtag;
-    }
-    if (!single) {
-      auto ca = make_ctx(h, dpgo::FLAG_NONE, nullptr);
-      HIP_TRY(dpgo::launch_accept(r, b, ca, h->x2.p, h->g2.p, h->S2.p, h->x1.p, h->g.p, h->S.p));
-    } else if (!direct) {
-      // speculative output, queued before the host knows whether another Run follows: the agents whose
-      // outcome this Run decided write X_out = accepted ? x2 : X_in, once (X_out may alias X_in), and
-      // their |X_out - X_in|^2 partials into pc; agents that retry are written by a later Run
-      auto cs = make_ctx(h, dpgo::FLAG_DECIDED, h->pc.p);
-      cs.round = round;
-      HIP_TRY(dpgo::launch_select(r, b, cs, h->x2.p, X_in, nullptr, X_in, X_out));
-    } else {
-      // x2 already sits in X_out: agents that did not move take X_in (queued before the retry
-      // decision; a retry Run retracts into X_out again and repeats this)
-      auto cm = make_ctx(h, dpgo::FLAG_MOVED, h->pa.p);
-      HIP_TRY(dpgo::launch_select(r, b, cm, X_in, X_in, nullptr, X_in, X_out));
-    }
-    if (round + 1 < max_rounds) {  // radius-shrink retry / next outer iteration needed?
-      bool any = false, any_cg = false, any_never = false;
-      DPGO_TRY(wait_published(h, rtag, &any, &any_cg, &any_never));
-      status_done = status_fold && !any_never && !any;
-      if (all_ahead || classic_ahead) h->predict_boundary = !any_cg;  // (published by the rho test: no status inside tCG)
-      if (!any) break;
-    }
-  }
-  // X_out: accepted candidate or the input (single Run), x1 (multi-iteration)
-  auto cs = make_ctx(h, dpgo::FLAG_NONE, h->pc.p);
-  if (!single) {
-    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->use_a.p), 1, K, h->stream));
-    HIP_TRY(dpgo::launch_select(r, b, cs, x1, X_in, h->use_a.p, X_in, X_out));
-  }
-  const bool want = results != nullptr || P.verbose;
-  // QuadraticOptimizer relativeChange against the input (the output select's partials, ref X_in)
-  if (want) DPGO_TRY(finalize(h, dpgo::OP_REL_CHANGE, h->pc.p, 1, nullptr, 0));
-  if (st && !status_done) {
-    // the output select left |X_out - X_in|^2 in pc: reuse it when the status reference is X_in
-    // itself (an in-place update without acceleration)
-    const bool reuse = st->ref == X_in && !direct;
-    DPGO_TRY(status_pass(h, X_out, *st, o, reuse ? h->pc.p : nullptr));
-  }
-  if (!want) return DPGO_HIP_OK;  // no host round trip needed
-  DPGO_TRY(download_state(h));
-  const double ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
-  if (results) {
-    for (int a = 0; a < K; ++a) {
-      fill_result(h->h_state[a], single, en[a] != 0, &results[a]);
-      results[a].elapsedMs = std::floor(ms);
-    }
-  }
-  if (P.verbose) {
-    for (int a = 0; a < K; ++a) {
-      const AgentState& s = h->h_state[a];
-      std::printf("[dpgo_hip] agent %d: f %.6g -> %.6g, |g| %.6g -> %.6g, runs %d, tCG %d (%d its)\n", a, s.f_init,
-                  single ? s.f2 : s.f1, s.ngf_init, single ? s.ngf2 : s.ngf, s.runs, s.tcg_status, s.tcg_iters);
-    }
-  }
-  return DPGO_HIP_OK;
-}
-
-// TUNE_SPLIT_STREAMS applies to batches of at least two agents and at most kSplitMaxTiles tiles: a small batch's
-// kernels leave the chip part-idle and two half-batch streams fill it (-4.6 % ms/step at the 125 k-pose share),
-// while at 1M (7,800 tiles per colour) the halves only share the chip (-0.7 %, within noise) and the per-launch
-// timing of one half beside the other would no longer be a kernel's own duration.
-bool dpgo::merged_split(dpgo_hip_problem h) {
-  constexpr int kSplitMaxTiles = 4096;
-  return h->K >= 2 && h->num_tiles <= kSplitMaxTiles && h->fuse_finalize == 0 &&
-         h->tuning[dpgo::TUNE_SPLIT_STREAMS] > 0;
-}
-
-// TUNE_TCG_BLOCK: the agent boundaries of the blocks the merged tCG loop is queued in, blocks[0] = 0 < ... <
-// blocks.back() = K.  Runs of consecutive agents formed greedily: an agent joins the current block while the block
-// stays within the target tile count, and a block has at least one agent (an agent larger than the target is a block
-// of its own).  Left with fewer than two blocks -- the unblocked queueing -- when the key is off, the finalize is fused
-// into the SpMM, or the whole batch fits in one block.
-void dpgo::merged_blocks(dpgo_hip_problem h, std::vector<int>* blocks) {
-  blocks->clear();
-  const int target = h->tuning[dpgo::TUNE_TCG_BLOCK];
-  if (target <= 0 || h->K < 2 || h->fuse_finalize != 0 || h->num_tiles <= target) return;
-  blocks->push_back(0);
-  int t_block = h->h_agent_tile_off[0];  // first tile of the current block
-  for (int a = 1; a < h->K; ++a)
-    if (h->h_agent_tile_off[a + 1] - t_block > target) {
-      blocks->push_back(a);
-      t_block = h->h_agent_tile_off[a];
-    }
-  blocks->push_back(h->K);
-}
 
 int dpgo_hip_tcg_blocks(dpgo_hip_problem h, int* blocks_last, int* agent_tiles) {
   DPGO_TRY(check_handle(h));

@@ -1,4 +1,4 @@
-// Internal (non-ABI) view of a dpgo_hip_problem, shared by capi.cpp and rbcd.cpp.
+// Internal (non-ABI) view of a dpgo_hip_problem, shared by capi.cpp, optimize.cpp and rbcd.cpp.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -182,11 +182,11 @@ struct dpgo_hip_problem_s {
   int precon = DPGO_PRECON_BLOCK_JACOBI;
 
   dpgo::ExactPrecond ex;  // exact preconditioner: supernodal Cholesky of Q + 0.1 I
-  dpgo::DevBuf<int4> tile_meta;
+  dpgo::DevBuf<int4> tile_meta;  // edge-stream Q: per tile stage ranges (LaunchCtx::tile_meta); empty otherwise
   // edge-stream records and diagonal blocks at unit weights (kept by the engine under a robust cost): the central
   // evaluation of examples/MultiRobotExample.cpp:229-235 reads the dataset's Q, not the reweighted one
   dpgo::DevBuf<double> rec_unit, diag_unit;
-  bool central_unit = false;  // qview() serves rec_unit / diag_unit  // edge-stream Q: per tile stage ranges (LaunchCtx::tile_meta); empty otherwise
+  bool central_unit = false;  // qview() serves rec_unit / diag_unit
   // host copy of the edge-stream incidences (sync_q_edges), for the factor's assembly tables
   std::vector<int> h_inc_ptr;
   std::vector<dpgo::SnPair> h_inc;
@@ -260,7 +260,7 @@ struct dpgo_hip_problem_s {
 
 
 namespace dpgo {
-// helpers implemented in capi.cpp
+// helpers implemented in capi.cpp (the optimiser driver and the block rules: optimize.cpp)
 // the launch context of the handle's next pose-tiled launch: its tile order comes from tile_order_next
 LaunchCtx make_ctx(dpgo_hip_problem h, int flag_kind, double* partials);
 LaunchCtx make_ctx_order(dpgo_hip_problem h, int flag_kind, double* partials, int order);
@@ -275,12 +275,12 @@ struct StatusArgs {
   const double* conv_ratio;
   double rel_tol, min_ratio;
 };
-// dpgo_hip_optimize_dev + the status pass (st may be null)
+// dpgo_hip_optimize_dev + the status pass (st may be null)  (optimize.cpp)
 int optimize_dev_status(dpgo_hip_problem h, const dpgo_opt_params* params, const double* X_in, double* X_out,
                         const int* agent_enabled_host, dpgo_opt_result* results, const StatusArgs* st);
+bool merged_split(dpgo_hip_problem h);  // TUNE_SPLIT_STREAMS applies to this batch (optimize.cpp, tcg_plan.h)
+void merged_blocks(dpgo_hip_problem h, std::vector<int>* blocks);  // TUNE_TCG_BLOCK's agent blocks (the same)
 // f / |grad|^2 / <G, X> per agent at X into the handle's sums (OP_SUM, nq 3): asynchronous
-bool merged_split(dpgo_hip_problem h);  // TUNE_SPLIT_STREAMS applies to this batch (capi.cpp)
-void merged_blocks(dpgo_hip_problem h, std::vector<int>* blocks);  // TUNE_TCG_BLOCK's agent blocks (capi.cpp)
 int eval_sums_dev(dpgo_hip_problem h, const double* X);
 // the same with the edge-stream Q at unit weights (keep_unit_q: the copy taken before any reweighting)
 int eval_sums_unit_dev(dpgo_hip_problem h, const double* X);
@@ -295,6 +295,30 @@ int take_spmm_times(dpgo_hip_problem h, double* ms_per_mode, long long* launches
 int drain_timed(dpgo_hip_problem h, bool wait);
 // one agent's Q as block-sparse rows, whichever format it was set in
 void agent_bsr(dpgo_hip_problem h, int a, HostBSR& out);
+
+// ---- launch helpers of capi.cpp that the optimiser driver (optimize.cpp) uses too
+// the arguments of one k_finalize launch over the whole batch (pub_kind 0: publishes no status word)
+FinalizeArgs make_fin(dpgo_hip_problem h, int op, const double* pa, int nqa, const double* pb, int nqb,
+                      const OptScalars* opt = nullptr, const int* enabled = nullptr, int pub_kind = 0, int pub_tag = 0,
+                      int agent_filter = 0);
+// make_fin + the launch on the handle's stream
+int finalize(dpgo_hip_problem h, int op, const double* pa, int nqa, const double* pb, int nqb,
+             const OptScalars* opt = nullptr, const int* enabled = nullptr, int pub_kind = 0, int pub_tag = 0,
+             int agent_filter = 0);
+// An SpMM followed by finalize `fin`: fused into the SpMM's last block per agent (spmm_arrive), or as
+// a separate k_finalize launch when fusion is off.
+int spmm_then_finalize(dpgo_hip_problem h, int mode, const LaunchCtx& c, SpmmArgs a, const FinalizeArgs& fin);
+// EVAL sweep at X: g = P_X(XQ+G), S, per-agent f and |g|^2 partials into pa.  mode MODE_F: f only;
+// MODE_EVAL_TCG: also the tCG start delta = -Prec(g) and the <z, g> partial.  fin: the finalize that follows it.
+int eval_at(dpgo_hip_problem h, const double* X, double* gout, double* Sout, double* part, int flag,
+            int mode = MODE_EVAL, double* delta = nullptr, int pmode = PRECON_NONE, const FinalizeArgs* fin = nullptr);
+// the next status tag of the handle (tags only grow: wait_published compares them with <)
+int next_tag(dpgo_hip_problem h);
+// spin on the host-mapped status words until every agent published `tag` or a later one; *any: some agent's flag is set
+int wait_published(dpgo_hip_problem h, int tag, bool* any, bool* any_cg = nullptr, bool* any_never = nullptr);
+// copy the agents' state / the per-agent sums into h_state / h_sums (synchronises)
+int download_state(dpgo_hip_problem h);
+int download_sums(dpgo_hip_problem h);
 
 // Events created for one scope and destroyed on every exit from it (an early HIP_TRY return included)
 struct ScopedEvents {

@@ -1349,7 +1349,7 @@ int dpgo_rbcd_bytes(dpgo_rbcd e, double* bytes, double* evaltcg_bytes_per_color)
   const double P = pose_bytes(e), b = e->b, d = e->d;
   const double blk = b * b * 8.0 + 4.0, DW = 8.0 * b * (b + 1) / 2, SW = 8.0 * d * (d + 1) / 2;
   double total = e->host_bytes;
-  // the merged tCG iteration (capi.cpp optimize_dev_status): HESS_M also reads r and Minv; k_tcg_updir
+  // the merged tCG iteration (optimize.cpp launch_merged_range): HESS_M also reads r and Minv; k_tcg_updir
   // replaces the update / direction pair and no z vector is written or read
   for (int c = 0; c < e->ncolors; ++c) {
     dpgo_hip_problem h = e->prob[c];

@@ -183,6 +183,19 @@ def test_cpp_sn_schedule(tmp_path):
         assert f"[PASS] {name}" in out, out[-3000:]
 
 
+def test_cpp_tcg_plan():
+    """The trust-region driver's plan (dpgo_amd/csrc/tcg_plan.h): the tCG flags and the queueing regime of a Run from
+    the optimiser parameters, the batch and the tuning keys.  Invariants over every combination of inputs, the
+    default keys' rows worked out by hand, and the agent-block rule on the batches test_gpu_tcg_block.py runs."""
+    binary = os.path.join(ROOT, "dpgo_amd", "cpp", "build", "test_tcg_plan")
+    assert os.path.exists(binary), "C++ tests not built (run __graft_entry__.build())"
+    p = subprocess.run([binary], capture_output=True, text=True, timeout=60)
+    out = p.stdout + p.stderr
+    assert p.returncode == 0, out[-3000:]
+    for name in ["Invariants", "NamedRows", "BlockRule"]:
+        assert f"[PASS] {name}" in out, out[-3000:]
+
+
 @pytest.mark.parametrize("name,agents", [("smallGrid3D", 5), ("input_INTEL_g2o", 4), ("city10000", 8)])
 def test_distributed_initialization_matches_oracle(H, name, agents):
     """PGOAgent::localInitialization per agent + initializeInGlobalFrame (host Cholesky path) vs the
