@@ -1614,6 +1614,81 @@ int dpgo_hip_rank_reduce(int r, int d, int n, const double* X, int k, const doub
   return download(X_out, o.p, kb * n, s);
 }
 
+// ----------------------------------------------------------------------- edge errors
+namespace {
+int check_edge_errors(int r, int d, long long n, const dpgo_edges* E, const void* X, const void* err,
+                      const void* rot_sq, const void* tra_sq, const void* cost) {
+  if ((d != 2 && d != 3) || r < d || !dpgo::supported_rb(r, d + 1))
+    return fail(DPGO_HIP_EINVAL, "edge_errors: unsupported (r, d)");
+  if (!E) return fail(DPGO_HIP_EINVAL, "edge_errors: null edge list");
+  if (E->m <= 0) return fail(DPGO_HIP_EINVAL, "edge_errors: need m >= 1 edges");
+  if (n <= 0) return fail(DPGO_HIP_EINVAL, "edge_errors: need n >= 1 poses");
+  if (!E->p1 || !E->p2 || !E->R || !E->t || !E->kappa || !E->tau || !X)
+    return fail(DPGO_HIP_EINVAL, "edge_errors: null p1, p2, R, t, kappa, tau or X");
+  if (!err && !rot_sq && !tra_sq && !cost) return fail(DPGO_HIP_EINVAL, "edge_errors: no output requested");
+  return DPGO_HIP_OK;
+}
+}  // namespace
+
+long long dpgo_hip_edge_errors_work_doubles(long long m) {
+  return m <= 0 ? 0 : static_cast<long long>(dpgo::edge_errors_blocks(static_cast<long>(m)));
+}
+
+int dpgo_hip_edge_errors_dev(int r, int d, long long n, const dpgo_edges* E_dev, const double* X_dev, double* err_dev,
+                             double* rot_sq_dev, double* tra_sq_dev, double* cost_dev, double* work_dev,
+                             void* stream) {
+  DPGO_TRY(check_edge_errors(r, d, n, E_dev, X_dev, err_dev, rot_sq_dev, tra_sq_dev, cost_dev));
+  if (cost_dev && !work_dev)
+    return fail(DPGO_HIP_EINVAL, "edge_errors: the cost needs a work buffer (dpgo_hip_edge_errors_work_doubles)");
+  if (usable_devices() == 0) return fail(DPGO_HIP_ENODEV, "no gfx950 device available (no CPU fallback)");
+  const dpgo::EdgeList L{static_cast<long>(E_dev->m), E_dev->p1, E_dev->p2, E_dev->R, E_dev->t, E_dev->kappa,
+                         E_dev->tau, E_dev->w};
+  HIP_TRY(dpgo::launch_edge_errors(r, d + 1, L, X_dev, nullptr, err_dev, rot_sq_dev, tra_sq_dev, cost_dev, work_dev,
+                                   static_cast<hipStream_t>(stream)));
+  return DPGO_HIP_OK;
+}
+
+int dpgo_hip_edge_errors(int r, int d, int n, const dpgo_edges* E, const double* X, double* err, double* rot_sq,
+                         double* tra_sq, double* cost) {
+  DPGO_TRY(check_edge_errors(r, d, n, E, X, err, rot_sq, tra_sq, cost));
+  const size_t m = static_cast<size_t>(E->m);
+  for (size_t k = 0; k < m; ++k) {
+    const int i = E->p1[k], j = E->p2[k];
+    if (i < 0 || i >= n || j < 0 || j >= n) return fail(DPGO_HIP_EINVAL, "edge_errors: pose index outside [0, n)");
+    if (i == j) return fail(DPGO_HIP_EINVAL, "edge_errors: an edge needs two different poses");
+  }
+  if (usable_devices() == 0) return fail(DPGO_HIP_ENODEV, "no gfx950 device available (no CPU fallback)");
+  const size_t rb = static_cast<size_t>(r) * (d + 1), dd = static_cast<size_t>(d) * d;
+  // one double buffer: measurements (R, t, kappa, tau, w), X, then the outputs (err, rot, tra, cost) and the partials
+  const size_t work = static_cast<size_t>(dpgo_hip_edge_errors_work_doubles(E->m));
+  const size_t o_R = 0, o_t = o_R + dd * m, o_k = o_t + d * m, o_tau = o_k + m, o_w = o_tau + m, o_X = o_w + m,
+               o_out = o_X + rb * n, total = o_out + 3 * m + 1 + work;
+  dpgo::DevBuf<double> buf;
+  dpgo::DevBuf<int> idx;
+  HIP_TRY(buf.ensure(total));
+  HIP_TRY(idx.ensure(2 * m));
+  hipStream_t s = nullptr;
+  HIP_TRY(hipMemcpyAsync(idx.p, E->p1, sizeof(int) * m, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(idx.p + m, E->p2, sizeof(int) * m, hipMemcpyHostToDevice, s));
+  DPGO_TRY(upload(buf.p + o_R, E->R, dd * m, s));
+  DPGO_TRY(upload(buf.p + o_t, E->t, d * m, s));
+  DPGO_TRY(upload(buf.p + o_k, E->kappa, m, s));
+  DPGO_TRY(upload(buf.p + o_tau, E->tau, m, s));
+  if (E->w) DPGO_TRY(upload(buf.p + o_w, E->w, m, s));
+  DPGO_TRY(upload(buf.p + o_X, X, rb * n, s));
+  double* out = buf.p + o_out;
+  const dpgo_edges L{E->m, idx.p, idx.p + m, buf.p + o_R, buf.p + o_t, buf.p + o_k, buf.p + o_tau,
+                     E->w ? buf.p + o_w : nullptr};
+  DPGO_TRY(dpgo_hip_edge_errors_dev(r, d, n, &L, buf.p + o_X, err ? out : nullptr, rot_sq ? out + m : nullptr,
+                                    tra_sq ? out + 2 * m : nullptr, cost ? out + 3 * m : nullptr, out + 3 * m + 1, s));
+  if (err) HIP_TRY(hipMemcpyAsync(err, out, sizeof(double) * m, hipMemcpyDeviceToHost, s));
+  if (rot_sq) HIP_TRY(hipMemcpyAsync(rot_sq, out + m, sizeof(double) * m, hipMemcpyDeviceToHost, s));
+  if (tra_sq) HIP_TRY(hipMemcpyAsync(tra_sq, out + 2 * m, sizeof(double) * m, hipMemcpyDeviceToHost, s));
+  if (cost) HIP_TRY(hipMemcpyAsync(cost, out + 3 * m, sizeof(double), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return DPGO_HIP_OK;
+}
+
 // ----------------------------------------------------------------------- certification
 }  // extern "C"
 

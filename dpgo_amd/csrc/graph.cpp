@@ -761,3 +761,13 @@ int dpgo_graph_rank_reduce(dpgo_graph g, int r, const double* X, double tol, int
   HIP_TRY(hipStreamSynchronize(s));
   return f_at(k, X_out, &info->f_after);
 }
+
+// The graph's own measurements through dpgo_hip_edge_errors: X r x (d+1) n at any compiled r >= d, a
+// lifted solution or, at r = d, a rounded trajectory; w per edge in the graph's order, or null for ones.
+int dpgo_graph_edge_errors(dpgo_graph g, int r, const double* X, const double* w, double* err, double* rot_sq,
+                           double* tra_sq, double* cost) {
+  if (!g || !X) return fail(DPGO_HIP_EINVAL, "edge_errors: null graph or X");
+  const dpgo_edges E{static_cast<long long>(g->p1.size()), g->p1.data(), g->p2.data(), g->R.data(), g->t.data(),
+                     g->kappa.data(), g->tau.data(), w};
+  return dpgo_hip_edge_errors(r, g->d, g->n, &E, X, err, rot_sq, tra_sq, cost);
+}

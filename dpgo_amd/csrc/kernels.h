@@ -473,6 +473,26 @@ struct RankW {
 };
 hipError_t launch_rank_project(int r, int k, int b, long n, const double* X, const RankW& W, double* out,
                                hipStream_t stream);
+// Edge errors (build-defined): per measurement e of the list, rot = |Y1 R - Y2|_F^2,
+// tra = |p2 - p1 - Y1 t|^2, err = kappa rot + tau tra (computeMeasurementError, src/DPGO_utils.cpp:509-515), and
+// cost = 1/2 sum_e w_e err_e.  A pose index s >= 0 reads pose s of X, s < 0 pose -1 - s of X2 (GncEntries'
+// encoding; X2 may be null when no index is negative).  Any of err, rot_sq, tra_sq, cost may be null, not all.  The
+// cost needs `work` (edge_errors_blocks(m) doubles): one partial per kEdgeErrThreads edges, then one finishing
+// launch that sums them in a fixed order.  No atomics: every output is a function of (list, X, X2) alone.
+struct EdgeList {
+  long m;
+  const int* p1;
+  const int* p2;
+  const double* R;  // d*d row-major
+  const double* t;
+  const double* kappa;
+  const double* tau;
+  const double* w;  // null: ones
+};
+constexpr int kEdgeErrThreads = 256;
+inline long edge_errors_blocks(long m) { return (m + kEdgeErrThreads - 1) / kEdgeErrThreads; }
+hipError_t launch_edge_errors(int r, int b, const EdgeList& E, const double* X, const double* X2, double* err,
+                              double* rot_sq, double* tra_sq, double* cost, double* work, hipStream_t stream);
 // PGOAgent::computeConvergedLoopClosureRatio (src/PGOAgent.cpp:1247-1289): per agent a, the share of
 // its loop closures idx[off[a] .. off[a+1]) whose weight w[] is exactly 1 or 0 (0/0 = NaN, as there)
 hipError_t launch_conv_ratio(int num_agents, const int* off, const int* idx, const double* w, double* ratio,

@@ -3099,6 +3099,103 @@ __global__ __launch_bounds__(64) void k_rank_project(long n, const double* __res
   }
 }
 
+// Edge errors (build-defined batch form of computeMeasurementError, src/DPGO_utils.cpp:509-515; DESIGN 3.13 and 7
+// item 13).  One thread per measurement e = (p1, p2, R, t, kappa, tau):
+//   rot = |Y1 R - Y2|_F^2,  tra = |p2 - p1 - Y1 t|^2,  err = kappa rot + tau tra,
+// the poses R x B column-major; an index s >= 0 is pose s of X, s < 0 pose -1 - s of X2 (GncEntries' encoding).
+// One operation order per (R, D), the same for every edge, block, pointer alignment and pose source:
+//   per row a: per column c, v = Y1[a,0] R[0,c], then D - 1 FMAs, df = v - Y2[a,c], rot = fma(df, df, rot);
+//              yt = Y1[a,0] t[0], then D - 1 FMAs, dt = (p2[a] - p1[a]) - yt, tra = fma(dt, dt, tra);
+//   err = (kappa rot) + (tau tra), each product rounded (no contraction).
+// rot is a chain of R D squares, tra of R.  With `partial` the block also leaves sum_e (0.5 w_e) err_e over its
+// kEdgeErrThreads edges (w NULL = ones; lanes past m add 0): k_gram's xor butterfly per wave, then thread 0 adds the wave
+// sums in wave order.  k_edge_cost_finish sums the partials.  No atomics, no LDS beyond the wave sums, no scratch.
+template <int R, int D>
+__global__ __launch_bounds__(kEdgeErrThreads) void k_edge_errors(long m, const int* __restrict__ p1, const int* __restrict__ p2,
+                                                          const double* __restrict__ Rm, const double* __restrict__ tv,
+                                                          const double* __restrict__ kappa,
+                                                          const double* __restrict__ tau, const double* __restrict__ w,
+                                                          const double* __restrict__ X, const double* __restrict__ X2,
+                                                          double* __restrict__ err, double* __restrict__ rot_sq,
+                                                          double* __restrict__ tra_sq, double* __restrict__ partial) {
+#pragma clang fp contract(off)
+  constexpr int B = D + 1;
+  __shared__ double ws[kEdgeErrThreads / 64];
+  const long e = static_cast<long>(blockIdx.x) * kEdgeErrThreads + threadIdx.x;
+  double term = 0.0;
+  if (e < m) {
+    const int s1 = p1[e], s2 = p2[e];
+    const double* P1 = s1 >= 0 ? X + static_cast<long>(s1) * (R * B) : X2 + static_cast<long>(-1 - s1) * (R * B);
+    const double* P2 = s2 >= 0 ? X + static_cast<long>(s2) * (R * B) : X2 + static_cast<long>(-1 - s2) * (R * B);
+    double Rr[D][D], tr[D];
+#pragma unroll
+    for (int u = 0; u < D; ++u) {
+#pragma unroll
+      for (int c = 0; c < D; ++c) Rr[u][c] = Rm[e * (D * D) + u * D + c];
+      tr[u] = tv[e * D + u];
+    }
+    double rot = 0.0, tra = 0.0;
+#pragma unroll
+    for (int a = 0; a < R; ++a) {
+      double y1[B];
+#pragma unroll
+      for (int u = 0; u < B; ++u) y1[u] = P1[u * R + a];
+#pragma unroll
+      for (int c = 0; c < D; ++c) {
+        double v = y1[0] * Rr[0][c];
+#pragma unroll
+        for (int u = 1; u < D; ++u) v = fma(y1[u], Rr[u][c], v);
+        const double df = v - P2[c * R + a];
+        rot = fma(df, df, rot);
+      }
+      double yt = y1[0] * tr[0];
+#pragma unroll
+      for (int u = 1; u < D; ++u) yt = fma(y1[u], tr[u], yt);
+      const double dt = (P2[D * R + a] - y1[D]) - yt;
+      tra = fma(dt, dt, tra);
+    }
+    const double kr = kappa[e] * rot, tt = tau[e] * tra;
+    const double er = kr + tt;
+    if (err) err[e] = er;
+    if (rot_sq) rot_sq[e] = rot;
+    if (tra_sq) tra_sq[e] = tra;
+    if (partial) term = (w ? 0.5 * w[e] : 0.5) * er;
+  }
+  if (partial == nullptr) return;  // uniform over the grid
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) term += __shfl_xor(term, off, 64);
+  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = term;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double s = ws[0];
+#pragma unroll
+    for (int k = 1; k < kEdgeErrThreads / 64; ++k) s += ws[k];
+    partial[blockIdx.x] = s;
+  }
+}
+
+// The cost from k_edge_errors' block partials, one block: thread t adds partials t, t + 1024, ... in that order,
+// the xor butterfly sums each wave, thread 0 adds the 16 wave sums in wave order.  A function of `blocks` alone.
+constexpr int kEdgeFinishThreads = 1024;
+__global__ __launch_bounds__(kEdgeFinishThreads) void k_edge_cost_finish(long blocks,
+                                                                         const double* __restrict__ partial,
+                                                                         double* __restrict__ cost) {
+  __shared__ double ws[kEdgeFinishThreads / 64];
+  const int t = static_cast<int>(threadIdx.x);
+  double v = 0.0;
+  for (long g = t; g < blocks; g += kEdgeFinishThreads) v += partial[g];
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+  if ((t & 63) == 0) ws[t >> 6] = v;
+  __syncthreads();
+  if (t == 0) {
+    double s = ws[0];
+#pragma unroll
+    for (int k = 1; k < kEdgeFinishThreads / 64; ++k) s += ws[k];
+    *cost = s;
+  }
+}
+
 // Nesterov updateV deferred into the colour's next combination pass (one pass instead of two):
 //   V' = project(V + gv (X - Yv))   (updateV, src/PGOAgent.cpp:1086-1091, of the agent's last update)
 //   out = project(sa X + sb V')     (updateY / the iterate(false) step, :1077-1084, of the next iteration)
@@ -5481,6 +5578,23 @@ hipError_t launch_rank_project(int r, int k, int b, long n, const double* X, con
   hipError_t e = hipSuccess;
   DPGO_DISPATCH(k, b, (e = rank_project_kb<R, B>(r, grid, n, X, W, out, stream)));
   return e != hipSuccess ? e : hipGetLastError();
+}
+
+hipError_t launch_edge_errors(int r, int b, const EdgeList& E, const double* X, const double* X2, double* err,
+                              double* rot_sq, double* tra_sq, double* cost, double* work, hipStream_t stream) {
+  if (E.m <= 0 || !E.p1 || !E.p2 || !E.R || !E.t || !E.kappa || !E.tau || X == nullptr) return hipErrorInvalidValue;
+  if (!err && !rot_sq && !tra_sq && !cost) return hipErrorInvalidValue;
+  if (cost != nullptr && work == nullptr) return hipErrorInvalidValue;
+  const long blocks = edge_errors_blocks(E.m);
+  if (blocks > 0x7fffffffL) return hipErrorInvalidValue;
+  const dim3 grid(static_cast<unsigned>(blocks));
+  double* partial = cost ? work : nullptr;
+  DPGO_DISPATCH(r, b, (k_edge_errors<R, B - 1><<<grid, kEdgeErrThreads, 0, stream>>>(
+                          E.m, E.p1, E.p2, E.R, E.t, E.kappa, E.tau, E.w, X, X2, err, rot_sq, tra_sq, partial)));
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess || !cost) return e;
+  k_edge_cost_finish<<<1, kEdgeFinishThreads, 0, stream>>>(blocks, work, cost);
+  return hipGetLastError();
 }
 
 hipError_t launch_sqdiff(int r, int b, const LaunchCtx& c, const double* A, const double* Bv) {

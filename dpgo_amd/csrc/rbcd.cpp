@@ -140,6 +140,19 @@ struct dpgo_rbcd_s {
   };
   std::vector<WMap> wmap;
   std::vector<int> odo_edges;  // graph edges that are odometry of an owned agent: weight 1, never reweighted
+  // edge errors (dpgo_rbcd_get_errors): the measurements dpgo_rbcd_get_weights reports for this rank (wmap's and
+  // odo_edges, in the order creation meets them) as graph edge, the two pose sources in GncEntries' sign encoding
+  // (>= 0 the owned buffer, -1 - slot the received poses) and R, t, kappa, tau.  Creation keeps the three ints per
+  // edge; the first call gathers the measurements from the graph and builds the device table (like agent_of_own).
+  dpgo_graph graph = nullptr;  // the creating graph: read again only by that first call
+  struct ErrTab {
+    std::vector<int> graph_edge, s1, s2;
+    DevBuf<int> src;      // s1 then s2
+    DevBuf<double> meas;  // R, t, kappa, tau
+    DevBuf<double> out;   // err, rot_sq, tra_sq per table entry
+    DevBuf<double> T;     // rounded: the owned poses, the received ones, then the caller's anchor
+    bool on_device = false;
+  } errtab;
 
   ~dpgo_rbcd_s();
   void release() {
@@ -580,6 +593,13 @@ int dpgo_rbcd_create(dpgo_graph g, int num_agents, const int* agent_of_pose, con
     if (q1 >= 0) agent_edges[q1].push_back(k);
     if (q2 >= 0 && q2 != q1) agent_edges[q2].push_back(k);
   }
+  auto err_entry = [&](size_t k, int s1, int s2) {
+    auto& T = e->errtab;
+    T.graph_edge.push_back(static_cast<int>(k));
+    T.s1.push_back(s1);
+    T.s2.push_back(s2);
+  };
+  e->graph = g;
   e->prob.assign(e->ncolors, nullptr);
   e->gt.assign(e->ncolors, nullptr);
   e->gnc.assign(e->ncolors, nullptr);
@@ -692,6 +712,7 @@ int dpgo_rbcd_create(dpgo_graph g, int num_agents, const int* agent_of_pose, con
         if (own_i && own_j) {
           if (local[j] == local[i] + 1) {  // odometry: never reweighted
             e->odo_edges.push_back(static_cast<int>(k));
+            err_entry(k, static_cast<int>(owned_index(i)), static_cast<int>(owned_index(j)));
             continue;
           }
         } else {
@@ -706,6 +727,7 @@ int dpgo_rbcd_create(dpgo_graph g, int num_agents, const int* agent_of_pose, con
           const long oi = owned_index(pose);
           return oi >= 0 ? static_cast<int>(oi) : -1 - static_cast<int>(recv_slot.at(pose));
         };
+        err_entry(k, src_of(i), src_of(j));
         gn_pe.push_back(static_cast<int>(prob_edges + static_cast<long>(x)));
         gn_ge.push_back(ge);
         gn_agent.push_back(q - a0);
@@ -988,6 +1010,82 @@ int dpgo_rbcd_get_X_reduced(dpgo_rbcd e, int k, const double* W, double* Xk) {
   HIP_TRY(hipStreamSynchronize(e->stream));
   for (long q = 0; q < e->Nown; ++q)
     std::memcpy(Xk + static_cast<size_t>(e->own_global[q]) * kbs, &host[q * kbs], sizeof(double) * kbs);
+  return DPGO_HIP_OK;
+}
+
+int dpgo_rbcd_get_errors(dpgo_rbcd e, const double* recv_dev, int rounded, const double* anchor, double* err,
+                         double* rot_sq, double* tra_sq) {
+  if (!e) return fail(DPGO_HIP_EINVAL, "null engine");
+  if (!err && !rot_sq && !tra_sq) return fail(DPGO_HIP_EINVAL, "get_errors: no output requested");
+  if (e->n_recv_poses > 0 && !recv_dev) return fail(DPGO_HIP_EINVAL, "get_errors: receive buffer required");
+  if (rounded && !anchor && e->own_of_global[0] < 0)
+    return fail(DPGO_HIP_EINVAL, "no anchor given and global pose 0 belongs to another rank (dpgo_rbcd_get_anchor)");
+  auto& T = e->errtab;
+  const size_t m = T.graph_edge.size();
+  if (m == 0) return DPGO_HIP_OK;  // a rank without poses reports nothing
+  DPGO_TRY(join_side(e));
+  const size_t d = static_cast<size_t>(e->d), dd = d * d, rbs = e->rb(), dbs = d * e->b;
+  if (!T.on_device) {
+    // gather the table's measurements from the graph's edge order: R, t, kappa, tau, each contiguous
+    const dpgo_graph g = e->graph;
+    std::vector<double> meas((dd + d + 2) * m);
+    double *hR = meas.data(), *ht = hR + dd * m, *hk = ht + d * m, *htau = hk + m;
+    for (size_t x = 0; x < m; ++x) {
+      const size_t k = static_cast<size_t>(T.graph_edge[x]);
+      std::memcpy(hR + x * dd, &g->R[k * dd], sizeof(double) * dd);
+      std::memcpy(ht + x * d, &g->t[k * d], sizeof(double) * d);
+      hk[x] = g->kappa[k];
+      htau[x] = g->tau[k];
+    }
+    HIP_TRY(T.src.ensure(2 * m));
+    HIP_TRY(T.meas.ensure((dd + d + 2) * m));
+    HIP_TRY(T.out.ensure(3 * m));
+    HIP_TRY(hipMemcpyAsync(T.src.p, T.s1.data(), sizeof(int) * m, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(T.src.p + m, T.s2.data(), sizeof(int) * m, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(T.meas.p, meas.data(), sizeof(double) * meas.size(), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));  // the staging vectors go away
+    std::vector<int>().swap(T.s1);
+    std::vector<int>().swap(T.s2);
+    T.on_device = true;
+  }
+  // the other ranks' poses of the shared edges, unpacked as dpgo_rbcd_central_eval does
+  if (e->n_recv_poses > 0)
+    HIP_TRY(launch_gather_poses(static_cast<int>(e->n_recv_poses), static_cast<int>(rbs), e->unpack_x.p, recv_dev,
+                                recv_dev, e->RXc.p, e->stream));
+  const double *P = e->X.p, *P2 = e->RXc.p;
+  int rank_k = e->r;
+  if (rounded) {
+    // rounding is per pose given the anchor: the received lifted poses round here to the bits their own rank gets
+    const size_t nr = static_cast<size_t>(e->n_recv_poses);
+    HIP_TRY(T.T.ensure((static_cast<size_t>(e->Nown) + nr) * dbs + rbs));
+    double* Town = T.T.p;
+    double* Trecv = Town + static_cast<size_t>(e->Nown) * dbs;
+    const double* anchor_dev = e->X.p + static_cast<size_t>(anchor ? 0 : e->own_of_global[0]) * rbs;
+    if (anchor) {
+      double* stage = Trecv + nr * dbs;
+      HIP_TRY(hipMemcpyAsync(stage, anchor, sizeof(double) * rbs, hipMemcpyHostToDevice, e->stream));
+      anchor_dev = stage;
+    }
+    DPGO_TRY(dpgo_hip_round_se_dev(e->r, e->d, e->Nown, e->X.p, anchor_dev, Town, e->stream));
+    if (nr) DPGO_TRY(dpgo_hip_round_se_dev(e->r, e->d, static_cast<long long>(nr), e->RXc.p, anchor_dev, Trecv, e->stream));
+    P = Town;
+    P2 = Trecv;
+    rank_k = e->d;
+  }
+  const double* q = T.meas.p;
+  const EdgeList L{static_cast<long>(m), T.src.p, T.src.p + m, q, q + dd * m, q + (dd + d) * m, q + (dd + d + 1) * m,
+                   nullptr};
+  double* outs[3] = {err, rot_sq, tra_sq};
+  HIP_TRY(launch_edge_errors(rank_k, e->b, L, P, P2, err ? T.out.p : nullptr, rot_sq ? T.out.p + m : nullptr,
+                             tra_sq ? T.out.p + 2 * m : nullptr, nullptr, nullptr, e->stream));
+  std::vector<double> host(3 * m);
+  for (int o = 0; o < 3; ++o)
+    if (outs[o])
+      HIP_TRY(hipMemcpyAsync(&host[o * m], T.out.p + o * m, sizeof(double) * m, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  for (int o = 0; o < 3; ++o)
+    if (outs[o])
+      for (size_t x = 0; x < m; ++x) outs[o][T.graph_edge[x]] = host[o * m + x];
   return DPGO_HIP_OK;
 }
 

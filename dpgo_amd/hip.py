@@ -62,6 +62,12 @@ class RankInfo(C.Structure):
     _fields_ = [("w", C.c_double * 8), ("dropped", C.c_double), ("f_before", C.c_double), ("f_after", C.c_double)]
 
 
+class Edges(C.Structure):
+    """dpgo_edges (include/dpgo_hip.h): host or device pointers, as the entry point says."""
+    _fields_ = [("m", C.c_longlong), ("p1", C.c_void_p), ("p2", C.c_void_p), ("R", C.c_void_p), ("t", C.c_void_p),
+                ("kappa", C.c_void_p), ("tau", C.c_void_p), ("w", C.c_void_p)]
+
+
 class DPGOHipError(RuntimeError):
     pass
 
@@ -115,6 +121,10 @@ _SIGS = [
     ("dpgo_hip_rank_reduce", [C.c_int, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp], C.c_int),
     ("dpgo_hip_rank_reduce_dev", [C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_int, _dp, C.c_void_p, C.c_void_p],
      C.c_int),
+    ("dpgo_hip_edge_errors", [C.c_int, C.c_int, C.c_int, C.POINTER(Edges), _dp, _dp, _dp, _dp, _dp], C.c_int),
+    ("dpgo_hip_edge_errors_work_doubles", [C.c_longlong], C.c_longlong),
+    ("dpgo_hip_edge_errors_dev", [C.c_int, C.c_int, C.c_longlong, C.POINTER(Edges), C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
     ("dpgo_hip_optimize", [C.c_void_p, C.POINTER(OptParams), _dp, _dp, C.POINTER(OptResult)], C.c_int),
     ("dpgo_hip_f_dev", [C.c_void_p, C.c_void_p, _dp], C.c_int),
     ("dpgo_hip_egrad_dev", [C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
@@ -722,6 +732,69 @@ def rank_reduce_dev(r, d, n, X_dev: int, W, X_out_dev: int, stream_ptr: int | No
                                           C.c_void_p(stream_ptr or 0)))
 
 
+def _edge_outputs(m, want):
+    """The output arrays of an edge_errors call: want = names among err, rot_sq, tra_sq, cost (None = all)."""
+    names = ("err", "rot_sq", "tra_sq", "cost")
+    want = names if want is None else tuple(want)
+    bad = [k for k in want if k not in names]
+    if bad:
+        raise DPGOHipError(f"edge_errors: unknown output {bad[0]}")
+    out = {k: np.empty(1 if k == "cost" else max(int(m), 1)) for k in want}
+    return out, [out[k].ctypes.data_as(_dp) if k in out else None for k in names]
+
+
+def _edge_result(out, m):
+    return {k: (float(v[0]) if k == "cost" else v[:m]) for k, v in out.items()}
+
+
+def edge_errors(X, d, p1, p2, R, t, kappa, tau, w=None, outputs=None):
+    """Per-measurement residuals of the poses X (r x (d+1) n: a lifted X or, at r = d, an SE(d) trajectory) on the
+    device: dict(err, rot_sq, tra_sq, cost) with rot_sq = |Y1 R - Y2|_F^2, tra_sq = |p2 - p1 - Y1 t|^2,
+    err = kappa rot_sq + tau tra_sq per edge and cost = 1/2 sum w err (w None = ones).  R: m x d x d (row-major per
+    edge), t: m x d.  outputs: the subset of those names to compute (None = all four)."""
+    X = np.asarray(X, dtype=np.float64)
+    r = X.shape[0]
+    n = X.shape[1] // (d + 1)
+    x, xp = _f64(to_dev_layout(X))
+    a1, _ = _i32(p1)
+    a2, _ = _i32(p2)
+    m = a1.size
+    Rr, _ = _f64(np.asarray(R).reshape(-1))
+    tt, _ = _f64(np.asarray(t).reshape(-1))
+    kk, _ = _f64(kappa)
+    ta, _ = _f64(tau)
+    if a2.size != m or Rr.size != m * d * d or tt.size != m * d or kk.size != m or ta.size != m:
+        raise DPGOHipError("edge_errors: p1, p2, R, t, kappa, tau must describe the same m edges")
+    ww = None
+    if w is not None:
+        ww, _ = _f64(w)
+        if ww.size != m:
+            raise DPGOHipError("edge_errors: w must have one entry per edge")
+    E = Edges(m, a1.ctypes.data, a2.ctypes.data, Rr.ctypes.data, tt.ctypes.data, kk.ctypes.data, ta.ctypes.data,
+              ww.ctypes.data if ww is not None else None)
+    out, ptrs = _edge_outputs(m, outputs)
+    _check(lib().dpgo_hip_edge_errors(r, d, n, C.byref(E), xp, *ptrs))
+    return _edge_result(out, m)
+
+
+def edge_errors_work_doubles(m) -> int:
+    """doubles of the work buffer edge_errors_dev needs for the cost of m edges."""
+    return int(lib().dpgo_hip_edge_errors_work_doubles(int(m)))
+
+
+def edge_errors_dev(r, d, n, m, p1_dev: int, p2_dev: int, R_dev: int, t_dev: int, kappa_dev: int, tau_dev: int,
+                    w_dev: int | None, X_dev: int, err_dev: int | None = None, rot_sq_dev: int | None = None,
+                    tra_sq_dev: int | None = None, cost_dev: int | None = None, work_dev: int | None = None,
+                    stream_ptr: int | None = None):
+    """edge_errors on device pointers (int32 indices, trusted; work_dev: edge_errors_work_doubles, needed with
+    cost_dev), queued on `stream_ptr` (None = the null stream) without synchronisation."""
+    E = Edges(int(m), p1_dev, p2_dev, R_dev, t_dev, kappa_dev, tau_dev, w_dev or None)
+    _check(lib().dpgo_hip_edge_errors_dev(int(r), int(d), int(n), C.byref(E), C.c_void_p(X_dev),
+                                          C.c_void_p(err_dev or 0), C.c_void_p(rot_sq_dev or 0),
+                                          C.c_void_p(tra_sq_dev or 0), C.c_void_p(cost_dev or 0),
+                                          C.c_void_p(work_dev or 0), C.c_void_p(stream_ptr or 0)))
+
+
 # ----------------------------------------------------------------------------------------
 # Pose graphs + multi-agent RBCD engine (include/dpgo_rbcd.h)
 # ----------------------------------------------------------------------------------------
@@ -779,6 +852,8 @@ _SIGS2 = [
     ("dpgo_graph_escape", [C.c_void_p, C.c_int, _dp, _dp, C.c_int, C.c_double, C.POINTER(EscapeParams), _dp,
                            C.POINTER(EscapeInfo)], C.c_int),
     ("dpgo_graph_rank_reduce", [C.c_void_p, C.c_int, _dp, C.c_double, _ip, _dp, C.POINTER(RankInfo)], C.c_int),
+    ("dpgo_graph_edge_errors", [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp], C.c_int),
+    ("dpgo_rbcd_get_errors", [C.c_void_p, C.c_void_p, C.c_int, _dp, _dp, _dp, _dp], C.c_int),
     ("dpgo_rbcd_gram", [C.c_void_p, _dp], C.c_int),
     ("dpgo_rbcd_get_X_reduced", [C.c_void_p, C.c_int, _dp, _dp], C.c_int),
     ("dpgo_chordal_initialization_gpu", [C.c_int, C.c_int, C.c_int, _ip, _ip, _dp, _dp, _dp, _dp, C.c_double,
@@ -1050,6 +1125,23 @@ class Graph:
         return k.value, out[:k.value * bn].copy(), dict(w=np.array(info.w[:r]), dropped=info.dropped,
                                                         f_before=info.f_before, f_after=info.f_after)
 
+    def edge_errors(self, X, r, w=None, outputs=None):
+        """hip.edge_errors over the graph's own measurements: X the flat r x (d+1) n column-major buffer (get_X_into,
+        trajectory_into at r = d) or the matrix, w per edge (None = ones; weights_into's array gives the cost a robust
+        run minimised).  dict(err [m], rot_sq [m], tra_sq [m], cost)."""
+        X = np.asarray(X, dtype=np.float64)
+        flat = np.ascontiguousarray(X.T).ravel() if X.ndim == 2 else np.ascontiguousarray(X).ravel()
+        if flat.size != r * (self.d + 1) * self.n:
+            raise DPGOHipError("X has the wrong size")
+        wp = None
+        if w is not None:
+            ww, wp = _f64(w)
+            if ww.size != self.m:
+                raise DPGOHipError("w must have one entry per edge")
+        out, ptrs = _edge_outputs(self.m, outputs)
+        _check(lib().dpgo_graph_edge_errors(self.h, int(r), flat.ctypes.data_as(_dp), wp, *ptrs))
+        return _edge_result(out, self.m)
+
     def grid_partition(self, agents_per_axis):
         out = np.empty(self.n, np.int32)
         _check(lib().dpgo_graph_grid_partition(self.h, int(agents_per_axis), out.ctypes.data_as(_ip)))
@@ -1289,6 +1381,29 @@ class Rbcd:
         if w.size < self.graph.m:
             raise ValueError(f"w holds {w.size} doubles, the graph has {self.graph.m} edges")
         _check(lib().dpgo_rbcd_get_weights(self.h, w.ctypes.data_as(_dp)))
+
+    def errors_into(self, err, recv_ptr=None, rounded=False, anchor=None, rot_sq=None, tra_sq=None):
+        """The residual err = kappa rot_sq + tau tra_sq of every measurement weights_into reports for this rank, at the
+        engine's current X, at its index in the graph's edge order (other entries untouched); rot_sq / tra_sq
+        likewise when given (err may be None then).  recv_ptr: the received public poses of a pack and exchange done
+        after the last update (required when this rank receives poses).  rounded: the errors of the rounded
+        trajectory in the frame of `anchor` (r x (d+1); None = global pose 0, which this rank must own), bitwise
+        Graph.edge_errors(T, d) of trajectory_into's T."""
+        ptrs = []
+        for a in (err, rot_sq, tra_sq):
+            if a is None:
+                ptrs.append(None)
+                continue
+            assert a.dtype == np.float64 and a.flags.c_contiguous
+            if a.size < self.graph.m:
+                raise ValueError(f"the array holds {a.size} doubles, the graph has {self.graph.m} edges")
+            ptrs.append(a.ctypes.data_as(_dp))
+        ap = None
+        if anchor is not None:
+            a, ap = _f64(to_dev_layout(anchor))
+            if a.size != self.params.r * (self.graph.d + 1):
+                raise ValueError("anchor must be r x (d+1)")
+        _check(lib().dpgo_rbcd_get_errors(self.h, C.c_void_p(recv_ptr or 0), 1 if rounded else 0, ap, *ptrs))
 
     def reset_stream(self):
         _check(lib().dpgo_rbcd_reset_stream(self.h))

@@ -361,6 +361,35 @@ int dpgo_hip_rank_reduce(int r, int d, int n, const double* X, int k, const doub
 int dpgo_hip_rank_reduce_dev(int r, int d, long long n, const double* X_dev, int k, const double* W,
                              double* X_out_dev, void* stream);
 
+/* ---- edge errors (the batch form of computeMeasurementError, src/DPGO_utils.cpp:509-515; the reference has the
+ * per-edge function only: pinned against a long double restatement) -------------------------------------
+ * For measurement e = (p1, p2, R, t, kappa, tau) and poses [Y_j | p_j] of r x (d+1) doubles (X column-major, a
+ * lifted X or, at r = d, an SE(d) trajectory):
+ *   rot_sq[e] = |Y_p1 R - Y_p2|_F^2,  tra_sq[e] = |p_p2 - p_p1 - Y_p1 t|^2,
+ *   err[e] = kappa rot_sq[e] + tau tra_sq[e],  *cost = 1/2 sum_e w_e err[e]   (w NULL = ones).
+ * With the weights Q was built from, cost = f(X) = 1/2 <Q, X^T X>.  One edge-parallel kernel; err[e] depends on
+ * the measurement and its two poses alone, through one operation order per (r, d): equal inputs give bitwise
+ * equal errors wherever the edge stands in the list.  The cost is one partial per 256 edges and one finishing
+ * launch that sums the partials in a fixed order (no atomics): a function of (edge list in its order, X, w),
+ * bitwise repeatable.  Any of err, rot_sq, tra_sq, cost may be NULL, not all four.  DPGO_HIP_EINVAL for an
+ * unsupported (r, d), m <= 0, n <= 0, a null required pointer, p1 == p2 or an index outside [0, n); the outputs are
+ * then untouched. */
+typedef struct {                 /* R row-major d*d per edge, t d per edge, as dpgo_graph_copy_out */
+  long long m;
+  const int *p1, *p2;
+  const double *R, *t, *kappa, *tau, *w;   /* w NULL = ones */
+} dpgo_edges;
+int dpgo_hip_edge_errors(int r, int d, int n, const dpgo_edges* E, const double* X,
+                         double* err, double* rot_sq, double* tra_sq, double* cost);
+/* doubles of the work buffer dpgo_hip_edge_errors_dev needs for the cost of m edges (0 for m <= 0) */
+long long dpgo_hip_edge_errors_work_doubles(long long m);
+/* the same on device pointers, queued on `stream` (hipStream_t or NULL), no synchronisation.  E_dev's arrays are
+ * device pointers, the struct itself is host memory; the indices are trusted.  work_dev
+ * (dpgo_hip_edge_errors_work_doubles) is needed only with cost_dev. */
+int dpgo_hip_edge_errors_dev(int r, int d, long long n, const dpgo_edges* E_dev, const double* X_dev,
+                             double* err_dev, double* rot_sq_dev, double* tra_sq_dev,
+                             double* cost_dev, double* work_dev, void* stream);
+
 /* ---- measurement helpers ----------------------------------------------------------------*/
 /* Select a compiled kernel variant / host sequence for A/B timing (process-wide; every setting gives
  * results within the documented bars, most bitwise the default's).  key 0: BSR X.Q SpMM

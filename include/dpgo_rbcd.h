@@ -162,6 +162,13 @@ typedef struct {
 } dpgo_rank_info;
 int dpgo_graph_rank_reduce(dpgo_graph g, int r, const double* X, double tol, int* k, double* X_out,
                            dpgo_rank_info* info);
+/* dpgo_hip_edge_errors (include/dpgo_hip.h) over the graph's own measurements: X r x (d+1) n column-major at any
+ * compiled r >= d -- a lifted solution or, at r = d, a rounded trajectory (dpgo_hip_round_se, dpgo_rbcd_get_trajectory)
+ * -- and w per edge in the graph's order (NULL = ones; dpgo_rbcd_get_weights' array gives the cost a robust run
+ * minimised).  err, rot_sq, tra_sq (m each) and cost (1) may each be NULL, not all.  With the weights Q was built
+ * from, *cost = f(X).  The caller compares err against its own threshold (barc^2). */
+int dpgo_graph_edge_errors(dpgo_graph g, int r, const double* X, const double* w,
+                           double* err, double* rot_sq, double* tra_sq, double* cost);
 int dpgo_graph_grid_partition(dpgo_graph g, int agents_per_axis, int* agent_of_pose);
 
 /* ---- RBCD engine ----------------------------------------------------------------------------*/
@@ -260,6 +267,22 @@ int dpgo_rbcd_get_X_reduced(dpgo_rbcd e, int k, const double* W, double* Xk_glob
  * lives on this rank; odometry (owner -1) is written by the rank of its agent, always 1.  With
  * robust_cost L2 every written entry is exactly 1. */
 int dpgo_rbcd_get_weights(dpgo_rbcd e, double* w);
+/* The residuals behind those weights: err = kappa |Y1 R - Y2|_F^2 + tau |p2 - p1 - Y1 t|^2 (and its two parts) of
+ * exactly the measurements dpgo_rbcd_get_weights reports for this rank, at the engine's current X after whatever is
+ * queued on its stream, written at their index in the graph's edge order (err, rot_sq, tra_sq of m doubles, each
+ * may be NULL, not all; other entries untouched).  One dpgo_hip_edge_errors launch over a per-rank table (graph
+ * edge, pose sources, measurement) that the first call builds: it reads the measurements of the graph the engine
+ * was created from, which must still exist then (not needed by later calls, nor by an engine that never asks).  A shared edge's other endpoint is read
+ * from the same rank's X or from recv_dev: a dpgo_rbcd_pack and exchange done after the last update, unpacked as
+ * dpgo_rbcd_central_eval unpacks it; required when this rank receives poses, else EINVAL.
+ * rounded = 0: the lifted errors.  rounded = 1: the errors of the rounded trajectory -- the owned poses and the
+ * received ones are rounded by dpgo_hip_round_se_dev in the frame of `anchor` (r x (d+1), host; NULL = global pose
+ * 0, which this rank must then own, else EINVAL, as dpgo_rbcd_get_trajectory) and the kernel runs at r = d.  Rounding
+ * is per pose given the anchor, so no second exchange of rounded poses takes place, and the merged result is
+ * bitwise dpgo_graph_edge_errors of the merged dpgo_rbcd_get_trajectory.  Synchronises.  On EINVAL the outputs are
+ * untouched. */
+int dpgo_rbcd_get_errors(dpgo_rbcd e, const double* recv_dev, int rounded, const double* anchor,
+                         double* err, double* rot_sq, double* tra_sq);
 /* host-only: the agent whose weight dpgo_rbcd_get_weights reports per edge (owner[m]); -1 = odometry
  * (both poses in one agent at consecutive local indices), never reweighted, weight 1.  A private loop
  * closure: its agent.  A shared loop closure: the lower-ID agent of the two -- the only copy
