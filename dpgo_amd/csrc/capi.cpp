@@ -385,6 +385,7 @@ int sync_q(dpgo_hip_problem h) {
   if (!h->q_dirty) return DPGO_HIP_OK;
   h->ex.state = 0;  // the exact preconditioner follows Q (setQ refactorises, :37-41)
   h->ex.sym_ready = false;  // a new Q may have a new pattern
+  h->cert.sym_ready = false;
   const int f0 = h->q_fmt[0];
   for (int a = 1; a < h->K; ++a)
     if (h->q_fmt[a] != f0) return fail(DPGO_HIP_ESTATE, "agents of one handle mix BSR and edge-stream Q");

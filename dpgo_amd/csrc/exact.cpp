@@ -6,8 +6,10 @@
 // one work list per tree level shared by the batch (level l of every agent runs in one launch per sweep).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <cstddef>
 #include <cstdio>
 #include <cstdlib>
@@ -108,10 +110,12 @@ int device_factor(dpgo_hip_problem h) {
   const bool verbose = verbose_chol();
   ScopedEvents lev(verbose ? maxd + 2 : 0);
   HIP_TRY(lev.create());
+  // the matrix: Q + 0.1 I (the preconditioner), or S(X) + shift I through the certificate's diagonal blocks
+  const double* diag = ex.use_cert_diag ? ex.cert_diag.p : h->diag.p;
   for (int dep = maxd; dep >= 0; --dep) {
     const int n0 = ex.level_off[dep], n1 = ex.level_off[dep + 1];
     SnFactorView v{ex.fac_nodes.p + n0, ex.s.p, ex.t.p, ex.fac_off.p, ex.panel_off.p, ex.poses_off.p, ex.poses.p,
-                   ex.ch_off.p, ex.ch.p, ex.tp_off.p, ex.tp.p, ex.ent_off.p, ex.ent.p, ex.src.p, h->rec.p, h->diag.p, 0.1,
+                   ex.ch_off.p, ex.ch.p, ex.tp_off.p, ex.tp.p, ex.ent_off.p, ex.ent.p, ex.src.p, h->rec.p, diag, ex.shift,
                    ex.fac_F[dep & 1].p, ex.fac_F[(dep + 1) & 1].p, ex.panel.p, ex.node_agent.p, ex.not_pd.p};
     if (verbose) HIP_TRY(hipEventRecord(lev.ev[dep + 1], h->stream));
     if (dep < static_cast<int>(ex.fac_seq.size()) && !ex.fac_seq[dep].empty()) {
@@ -405,7 +409,7 @@ int sync_chol(dpgo_hip_problem h) {
   if (ex.state != 0) return DPGO_HIP_OK;
   bool edges = true;
   for (int a = 0; a < h->K; ++a) edges = edges && h->q_fmt[a] == QFMT_EDGES;
-  const bool device = edges && h->tuning[TUNE_DEVICE_CHOL] > 0;
+  const bool device = edges && (h->tuning[TUNE_DEVICE_CHOL] > 0 || ex.force_device);
   if (device && ex.sym_ready) return device_factor(h);  // same pattern: only the numeric half again, never waits
   if (!device) DPGO_TRY(refresh_host_weights(h));
   std::vector<SupernodalFactor> Fs;
@@ -450,11 +454,224 @@ int exact_precond(dpgo_hip_problem h, const double* in, double* z_out, double* d
   return DPGO_HIP_OK;
 }
 
+// ---- certification by factorisation: S(X) + sigma I through the factor kernels above
+namespace {
+
+// The certificate's factor state stands in h->ex for one scope, so sync_chol, device_factor and the sweeps run on it
+// unchanged; on every exit the preconditioner's state is back where it was
+struct CertScope {
+  dpgo_hip_problem h;
+  explicit CertScope(dpgo_hip_problem hh) : h(hh) {
+    std::swap(h->ex, h->cert);
+    h->ex.use_cert_diag = h->ex.force_device = true;
+  }
+  ~CertScope() { std::swap(h->ex, h->cert); }
+};
+
+int cert_check(dpgo_hip_problem h, const double* X) {
+  DPGO_TRY(check_handle(h));
+  if (h->K != 1) return fail(DPGO_HIP_EINVAL, "certification needs a single-agent handle");
+  if (!X) return fail(DPGO_HIP_EINVAL, "bad certification arguments");
+  DPGO_TRY(problem_ready(h));
+  if (h->q_fmt[0] != QFMT_EDGES)
+    return fail(DPGO_HIP_EINVAL, "certification by factorisation needs an edge-stream Q (set_Q_edges)");
+  return ensure_work_public(h);
+}
+
+// X to the device, Lambda(X) into h->S (the S the Riemannian Hessian uses), the certificate's diagonal blocks
+int cert_begin(dpgo_hip_problem h, const double* X, DevBuf<double>& xdev) {
+  HIP_TRY(xdev.ensure(h->vec_len()));
+  HIP_TRY(hipMemcpyAsync(xdev.p, X, h->vec_bytes(), hipMemcpyHostToDevice, h->stream));
+  DPGO_TRY(eval_at(h, xdev.p, h->tA.p, h->S.p, h->pa.p, FLAG_NONE));
+  HIP_TRY(h->ex.cert_diag.ensure(static_cast<size_t>(h->N) * diag_width(h->d)));
+  HIP_TRY(launch_cert_diag(h->b, static_cast<int>(h->N), h->diag.p, h->S.p, h->ex.cert_diag.p, h->stream));
+  return DPGO_HIP_OK;
+}
+
+// one numeric factorisation of S(X) + sigma I (the symbolic analysis on the first call per pattern); the one wait
+int cert_factor(dpgo_hip_problem h, double sigma, int* pd) {
+  auto& ex = h->ex;
+  ex.shift = sigma;
+  ex.state = 0;
+  DPGO_TRY(sync_chol(h));
+  int bad = 0;
+  HIP_TRY(hipMemcpyAsync(&bad, ex.not_pd.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  *pd = bad == 0;
+  return DPGO_HIP_OK;
+}
+
+}  // namespace
+
 }  // namespace dpgo
 
 using namespace dpgo;
 
 extern "C" {
+
+void dpgo_default_chol_cert_params(dpgo_chol_cert_params* p) {
+  if (!p) return;
+  p->ratio = 1.0 + 1.0 / 16.0;
+  p->max_factorisations = 24;
+  p->tol = 1e-8;
+  p->max_iters = 200;
+}
+
+int dpgo_hip_certify_chol(dpgo_hip_problem h, const double* X, double sigma, int* pd) {
+  DPGO_TRY(check_handle(h));
+  if (!pd || !std::isfinite(sigma)) return fail(DPGO_HIP_EINVAL, "bad certification arguments");
+  DPGO_TRY(cert_check(h, X));
+  CertScope scope(h);
+  DevBuf<double> xdev;
+  DPGO_TRY(cert_begin(h, X, xdev));
+  int ok = 0;
+  DPGO_TRY(cert_factor(h, sigma, &ok));
+  *pd = ok;
+  return DPGO_HIP_OK;
+}
+
+int dpgo_hip_certify_chol_ex(dpgo_hip_problem h, const double* X, double eta, const dpgo_chol_cert_params* p,
+                             double* lambda_min, double* eigvec, dpgo_chol_cert_info* info) {
+  DPGO_TRY(check_handle(h));
+  dpgo_chol_cert_params P;
+  dpgo_default_chol_cert_params(&P);
+  if (p) P = *p;
+  if (!lambda_min || !std::isfinite(eta) || !(eta > 0.0) || !(P.ratio > 1.0) || P.max_factorisations < 2 ||
+      !(P.tol > 0.0) || P.max_iters < 1)
+    return fail(DPGO_HIP_EINVAL, "bad certification arguments");
+  DPGO_TRY(cert_check(h, X));
+  CertScope scope(h);
+  auto& ex = h->ex;
+  DevBuf<double> xdev;
+  DPGO_TRY(cert_begin(h, X, xdev));
+  dpgo_chol_cert_info I{};
+  auto finish_info = [&]() -> int {
+    DPGO_TRY(resolve_factor_ms(h));
+    I.factor_ms = ex.factor_ms;
+    I.panel_doubles = ex.panel_doubles;
+    if (info) *info = I;
+    return DPGO_HIP_OK;
+  };
+  int pd = 0;
+  DPGO_TRY(cert_factor(h, eta, &pd));
+  I.factorisations = 1;
+  if (pd) {
+    I.certified = 1;
+    I.sigma_lo = I.sigma_hi = eta;
+    DPGO_TRY(finish_info());
+    *lambda_min = -eta;
+    return DPGO_HIP_OK;
+  }
+  // the bracket's top: S = Q - Lambda >= -max_j |Lambda_j|_2 I since Q >= 0
+  const long SW = (h->b - 1) * h->b / 2, D = h->b - 1;
+  std::vector<double> Sh(h->s_len());
+  HIP_TRY(hipMemcpyAsync(Sh.data(), h->S.p, sizeof(double) * Sh.size(), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  double fmax = 0.0;
+  for (long j = 0; j < h->N; ++j) {
+    double acc = 0.0;
+    long q = j * SW;
+    for (long u = 0; u < D; ++u)
+      for (long v = u; v < D; ++v, ++q) acc += (u == v ? 1.0 : 2.0) * Sh[q] * Sh[q];
+    fmax = std::max(fmax, acc);
+  }
+  const double sigma_top = (1.0 + 1e-6) * std::sqrt(fmax) + eta;
+  double lo = eta, hi = sigma_top;
+  DPGO_TRY(cert_factor(h, hi, &pd));
+  I.factorisations += 1;
+  if (!pd)
+    return fail(DPGO_HIP_EDEVICE, "certification: S(X) + sigma_top I is not positive definite (Q is not positive "
+                                  "semidefinite, or the factorisation broke down)");
+  bool at_hi = true;  // the factor in place is the one at `hi`
+  while (hi / lo > P.ratio && I.factorisations < P.max_factorisations) {
+    const double mid = std::sqrt(lo) * std::sqrt(hi);
+    if (!(mid > lo && mid < hi)) break;
+    DPGO_TRY(cert_factor(h, mid, &pd));
+    I.factorisations += 1;
+    (pd ? hi : lo) = mid;
+    at_hi = pd != 0;
+  }
+  if (!at_hi) {  // the last trial failed: the factor at sigma_hi again (over any max_factorisations, by one)
+    DPGO_TRY(cert_factor(h, hi, &pd));
+    I.factorisations += 1;
+    if (!pd) return fail(DPGO_HIP_EDEVICE, "certification: the factorisation at sigma_hi did not repeat");
+  }
+  I.sigma_lo = lo;
+  I.sigma_hi = hi;
+  // inverse iteration on row 0 of the lifted layout (rows 1.. are zero and stay zero: the solve acts row by row);
+  // vy = [v | y = v S] so one launch_dot_multi gives <y, v> and <y, y>
+  const long L = static_cast<long>(h->vec_len());
+  const int r = h->r;
+  DevBuf<double> vy, part, coef;
+  HIP_TRY(vy.ensure(2 * static_cast<size_t>(L)));
+  HIP_TRY(part.ensure(static_cast<size_t>(kDotBlocks) * 2));
+  HIP_TRY(coef.ensure(1));
+  double* v = vy.p;
+  double* y = vy.p + L;
+  auto dots = [&](const double* x, const double* B, int k, double* out) -> int {
+    HIP_TRY(launch_dot_multi(L, x, B, k, part.p, h->stream));
+    std::vector<double> hp(static_cast<size_t>(kDotBlocks) * k);
+    HIP_TRY(hipMemcpyAsync(hp.data(), part.p, sizeof(double) * hp.size(), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    for (int j = 0; j < k; ++j) out[j] = 0.0;
+    for (int g = 0; g < kDotBlocks; ++g)
+      for (int j = 0; j < k; ++j) out[j] += hp[static_cast<size_t>(g) * k + j];
+    return DPGO_HIP_OK;
+  };
+  {  // seeded start (SplitMix64 uniform in [-1, 1), the Lanczos certificate's stream) on row 0
+    std::vector<double> q0(L, 0.0);
+    unsigned long long st = 0x5EEDULL;
+    for (long x = 0; x < L; x += r) {
+      st += 0x9E3779B97F4A7C15ULL;
+      unsigned long long z = st;
+      z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+      z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+      z ^= z >> 31;
+      q0[x] = 2.0 * (static_cast<double>(z >> 11) * (1.0 / 9007199254740992.0)) - 1.0;
+    }
+    HIP_TRY(hipMemcpyAsync(v, q0.data(), sizeof(double) * L, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+  }
+  const SnView view = sn_view(h, FLAG_NONE);
+  double lam = 0.0, res = 0.0;
+  int it = 0;
+  while (it < P.max_iters) {
+    if (poison_enabled())  // debug: frontal / update / sweep vectors as nothing-written NaN
+      for (auto* B : {&ex.F, &ex.U, &h->tA, &h->tB}) HIP_TRY(poison_fill(B->p, sizeof(double) * B->n, h->stream));
+    DPGO_TRY(sweep_forward(h, view, v));
+    DPGO_TRY(sweep_backward(h, view));
+    ++it;
+    double nn = 0.0;
+    DPGO_TRY(dots(h->tB.p, h->tB.p, 1, &nn));
+    if (!(nn > 0.0) || !std::isfinite(nn))
+      return fail(DPGO_HIP_EDEVICE, "certification: the inverse iteration broke down");
+    HIP_TRY(launch_scale(L, h->tB.p, 1.0 / std::sqrt(nn), v, h->stream));
+    const SpmmArgs sa{v, nullptr, nullptr, nullptr, h->S.p, y, nullptr, nullptr, nullptr, PRECON_NONE};
+    DPGO_TRY(spmm_launch(h, MODE_CERT, make_ctx(h, FLAG_NONE, nullptr), sa));
+    double d2[2];
+    DPGO_TRY(dots(y, vy.p, 2, d2));  // <y, v>, <y, y>
+    lam = d2[0];
+    // the residual y - lam v itself (|y|^2 - lam^2 cancels where the pair has converged)
+    HIP_TRY(hipMemcpyAsync(coef.p, &lam, sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(launch_axpy_multi(L, y, v, 1, coef.p, h->stream));
+    double rr = 0.0;
+    DPGO_TRY(dots(y, y, 1, &rr));
+    res = std::sqrt(std::max(rr, 0.0));
+    if (res <= P.tol * sigma_top) break;
+  }
+  I.invit_iters = it;
+  I.residual = res;
+  std::vector<double> ev;
+  if (eigvec) {
+    ev.resize(L);
+    HIP_TRY(hipMemcpyAsync(ev.data(), v, sizeof(double) * L, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+  }
+  DPGO_TRY(finish_info());
+  if (eigvec) std::copy(ev.begin(), ev.end(), eigvec);
+  *lambda_min = lam;
+  return DPGO_HIP_OK;
+}
 
 int dpgo_hip_exact_factor_info(dpgo_hip_problem h, long long* nodes, int* levels, int* max_s_tiles,
                                long long* panel_doubles, double* factor_ms, int* factor_count) {

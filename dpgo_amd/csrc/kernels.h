@@ -548,6 +548,9 @@ hipError_t launch_scale(long len, const double* src, double s, double* dst, hipS
 hipError_t launch_strided_copy(long len, const double* src, int src_stride, double* dst, int dst_stride,
                                hipStream_t stream);
 hipError_t launch_bj_inverse_diag(int b, int n, const QView& q, double shift, double* Minv, hipStream_t stream);
+// The certificate matrix's packed diagonal blocks: out_j = diag_j - [S_j 0; 0 0] per pose (diag: diag_width(d)
+// doubles per pose, S: the packed d x d sym(Y_j^T (XQ+G)_Y) an EVAL pass leaves).  out must not alias diag.
+hipError_t launch_cert_diag(int b, int n, const double* diag, const double* S, double* out, hipStream_t stream);
 
 // ---- Jacobi-PCG on SPD block-sparse systems with several right-hand sides (GPU chordal
 // initialisation, init.cpp).  Vectors are [row][bs][nr]: row p holds bs x nr doubles (column a of

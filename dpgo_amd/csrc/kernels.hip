@@ -3721,6 +3721,24 @@ __global__ __launch_bounds__(kThreads) void k_bj_inverse_diag(int n, QView q, do
     for (int w = u; w < B; ++w) Minv[j * diag_width(B - 1) + minv_index<B>(u, w)] = A[u][B + w];
 }
 
+// The certificate matrix's diagonal blocks (one thread per pose): S(X) = Q - Lambda(X), Lambda block-diagonal with
+// pose j's packed sym(Y_j^T (XQ+G)_Y) (the S an EVAL pass leaves) in the rotation part and zero in the translation
+// row / column.  out may not alias diag.
+template <int B>
+__global__ __launch_bounds__(kThreads) void k_cert_diag(int n, const double* __restrict__ diag,
+                                                        const double* __restrict__ S, double* __restrict__ out) {
+  constexpr int D = B - 1, DW = diag_width(D), SW = s_width(D);
+  const long j = static_cast<long>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+#pragma unroll
+  for (int u = 0; u < B; ++u)
+#pragma unroll
+    for (int v = u; v < B; ++v) {
+      const double lam = (u < D && v < D) ? S[j * SW + sym_index<D>(u < D ? u : 0, v < D ? v : 0)] : 0.0;
+      out[j * DW + sym_index<B>(u, v)] = diag[j * DW + sym_index<B>(u, v)] - lam;
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // On-device Q assembly from edge weights (PGOAgent::constructQMatrix after a GNC weight update,
 // src/PGOAgent.cpp:720-781, 1181-1244).  raw per slot = [R (row-major) | t | kappa | tau]; the
@@ -5881,6 +5899,18 @@ hipError_t launch_bj_inverse_diag(int b, int n, const QView& q, double shift, do
     k_bj_inverse_diag<3><<<blocks, kThreads, 0, stream>>>(n, q, shift, Minv);
   else if (b == 4)
     k_bj_inverse_diag<4><<<blocks, kThreads, 0, stream>>>(n, q, shift, Minv);
+  else
+    return hipErrorInvalidValue;
+  return hipGetLastError();
+}
+
+hipError_t launch_cert_diag(int b, int n, const double* diag, const double* S, double* out, hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  const int blocks = (n + kThreads - 1) / kThreads;
+  if (b == 3)
+    k_cert_diag<3><<<blocks, kThreads, 0, stream>>>(n, diag, S, out);
+  else if (b == 4)
+    k_cert_diag<4><<<blocks, kThreads, 0, stream>>>(n, diag, S, out);
   else
     return hipErrorInvalidValue;
   return hipGetLastError();

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <map>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/dpgo_hip.h"
@@ -56,6 +57,16 @@ struct DevBuf {
   DevBuf() = default;
   DevBuf(const DevBuf&) = delete;
   DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), n(o.n), alloc_flags(o.alloc_flags) {
+    o.p = nullptr;
+    o.n = 0;
+  }
+  DevBuf& operator=(DevBuf&& o) noexcept {  // by exchange: o leaves with this buffer's allocation
+    std::swap(p, o.p);
+    std::swap(n, o.n);
+    std::swap(alloc_flags, o.alloc_flags);
+    return *this;
+  }
   ~DevBuf() { release(); }
   void release() {
     if (p) (void)hipFree(p);
@@ -79,6 +90,27 @@ struct DevBuf {
     const hipError_t f = poison_fill(p, n * sizeof(T), nullptr);
     return f != hipSuccess ? f : hipDeviceSynchronize();
   }
+};
+
+// A pair of events owned by its holder, movable with it (the device factorisation's timing window)
+struct EventPair {
+  hipEvent_t e[2] = {nullptr, nullptr};
+  EventPair() = default;
+  EventPair(const EventPair&) = delete;
+  EventPair& operator=(const EventPair&) = delete;
+  EventPair(EventPair&& o) noexcept : e{o.e[0], o.e[1]} { o.e[0] = o.e[1] = nullptr; }
+  EventPair& operator=(EventPair&& o) noexcept {
+    std::swap(e[0], o.e[0]);
+    std::swap(e[1], o.e[1]);
+    return *this;
+  }
+  ~EventPair() {
+    for (auto x : e)
+      if (x) (void)hipEventDestroy(x);
+  }
+  hipEvent_t& operator[](int i) { return e[i]; }
+  hipEvent_t* begin() { return e; }
+  hipEvent_t* end() { return e + 2; }
 };
 
 // The exact preconditioner's device state (exact.cpp): supernodal Cholesky of Q + 0.1 I (chol.cpp), one launch per
@@ -124,11 +156,13 @@ struct ExactPrecond {
   double factor_ms = 0.0;       // the last device factorisation (hipEvent), for the benches
   bool factor_pending = false;  // fac_ev holds a factorisation whose time is not yet in factor_ms
   int factor_count = 0;
-  hipEvent_t fac_ev[2] = {nullptr, nullptr};  // the device factorisation's timing (created once per handle)
-  ~ExactPrecond() {
-    for (auto e : fac_ev)
-      if (e) (void)hipEventDestroy(e);
-  }
+  EventPair fac_ev;  // the device factorisation's timing (created once per handle)
+  // What the factor is of: Q + 0.1 I from the handle's diagonal blocks (the preconditioner), or, for the
+  // certificate's state (dpgo_hip_problem_s::cert), S(X) + shift I from the diagonal blocks in cert_diag.
+  // force_device: the numeric factorisation runs on the device whatever TUNE_DEVICE_CHOL says.
+  double shift = 0.1;
+  DevBuf<double> cert_diag;
+  bool use_cert_diag = false, force_device = false;
 };
 
 }  // namespace dpgo
@@ -182,6 +216,9 @@ struct dpgo_hip_problem_s {
   int precon = DPGO_PRECON_BLOCK_JACOBI;
 
   dpgo::ExactPrecond ex;  // exact preconditioner: supernodal Cholesky of Q + 0.1 I
+  // the Cholesky certificate's factor of S(X) + sigma I (dpgo_hip_certify_chol*): exchanged with `ex` around its
+  // calls, so the preconditioner's factor, flags and counters never see it
+  dpgo::ExactPrecond cert;
   dpgo::DevBuf<int4> tile_meta;  // edge-stream Q: per tile stage ranges (LaunchCtx::tile_meta); empty otherwise
   // edge-stream records and diagonal blocks at unit weights (kept by the engine under a robust cost): the central
   // evaluation of examples/MultiRobotExample.cpp:229-235 reads the dataset's Q, not the reweighted one

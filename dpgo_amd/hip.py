@@ -62,6 +62,21 @@ class RankInfo(C.Structure):
     _fields_ = [("w", C.c_double * 8), ("dropped", C.c_double), ("f_before", C.c_double), ("f_after", C.c_double)]
 
 
+class CholCertParams(C.Structure):
+    """dpgo_chol_cert_params (include/dpgo_hip.h)."""
+    _fields_ = [("ratio", C.c_double), ("max_factorisations", C.c_int), ("tol", C.c_double), ("max_iters", C.c_int)]
+
+
+class CholCertInfo(C.Structure):
+    """dpgo_chol_cert_info (include/dpgo_hip.h)."""
+    _fields_ = [("certified", C.c_int), ("factorisations", C.c_int), ("sigma_lo", C.c_double),
+                ("sigma_hi", C.c_double), ("invit_iters", C.c_int), ("residual", C.c_double),
+                ("factor_ms", C.c_double), ("panel_doubles", C.c_longlong)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class Edges(C.Structure):
     """dpgo_edges (include/dpgo_hip.h): host or device pointers, as the entry point says."""
     _fields_ = [("m", C.c_longlong), ("p1", C.c_void_p), ("p2", C.c_void_p), ("R", C.c_void_p), ("t", C.c_void_p),
@@ -69,7 +84,7 @@ class Edges(C.Structure):
 
 
 class DPGOHipError(RuntimeError):
-    pass
+    code = 0  # the C ABI's return code where one raised it
 
 
 _lib = None
@@ -151,6 +166,10 @@ _SIGS = [
     ("dpgo_hip_certify", [C.c_void_p, _dp, C.c_int, C.c_double, _dp, _dp, _ip, _dp], C.c_int),
     ("dpgo_hip_certify_ex", [C.c_void_p, _dp, C.c_int, C.c_int, C.c_int, C.c_double, _dp, _dp, C.c_void_p],
      C.c_int),
+    ("dpgo_default_chol_cert_params", [C.POINTER(CholCertParams)], None),
+    ("dpgo_hip_certify_chol", [C.c_void_p, _dp, C.c_double, _ip], C.c_int),
+    ("dpgo_hip_certify_chol_ex", [C.c_void_p, _dp, C.c_double, C.POINTER(CholCertParams), _dp, _dp,
+                                  C.POINTER(CholCertInfo)], C.c_int),
     ("dpgo_hip_bench_hvp", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, _dp], C.c_int),
     ("dpgo_hip_stats", [C.c_void_p, _ip], C.c_int),
     ("dpgo_hip_set_trace", [C.c_void_p, C.c_int], C.c_int),
@@ -198,7 +217,20 @@ def lib():
 
 def _check(rc):
     if rc != 0:
-        raise DPGOHipError(f"dpgo_hip error {rc}: {lib().dpgo_hip_last_error().decode()}")
+        e = DPGOHipError(f"dpgo_hip error {rc}: {lib().dpgo_hip_last_error().decode()}")
+        e.code = rc
+        raise e
+
+
+def chol_cert_params(**kw) -> CholCertParams:
+    """dpgo_default_chol_cert_params with the given fields (ratio, max_factorisations, tol, max_iters) replaced."""
+    p = CholCertParams()
+    lib().dpgo_default_chol_cert_params(C.byref(p))
+    for k, v in kw.items():
+        if k not in dict(CholCertParams._fields_):
+            raise TypeError(f"unknown certificate parameter {k!r}")
+        setattr(p, k, v)
+    return p
 
 
 def _f64(a):
@@ -456,6 +488,30 @@ class Problem:
                                          C.byref(info)))
         self.last_certificate = info.as_dict()
         return lam.value, info.residual, info.iters, (from_dev_layout(v, self.r) if v is not None else None)
+
+    def certify_chol(self, X, sigma):
+        """True iff the device Cholesky factorisation of S(X) + sigma I met no non-positive pivot: lambda_min(S(X)) >
+        -sigma up to its backward error (dpgo_hip_certify_chol; single agent, edge-stream Q)."""
+        x, xp = self._in(X)
+        pd = C.c_int(-1)
+        _check(lib().dpgo_hip_certify_chol(self.h, xp, float(sigma), C.byref(pd)))
+        return bool(pd.value)
+
+    def certify_chol_ex(self, X, eta, want_vector=True, **params):
+        """The certificate by factorisation (dpgo_hip_certify_chol_ex): dict(lambda_min, certified, factorisations,
+        sigma_lo, sigma_hi, invit_iters, residual, factor_ms, panel_doubles[, eigvec r x (d+1) n: the unit vector on
+        row 0]).  Certified (S(X) + eta I positive definite): lambda_min = -eta, no eigvec.  params: the fields of
+        dpgo_chol_cert_params."""
+        x, xp = self._in(X)
+        lam, info = C.c_double(), CholCertInfo()
+        v = np.empty(self.vec_len) if want_vector else None
+        _check(lib().dpgo_hip_certify_chol_ex(self.h, xp, float(eta), C.byref(chol_cert_params(**params)),
+                                              C.byref(lam), v.ctypes.data_as(_dp) if v is not None else None,
+                                              C.byref(info)))
+        out = dict(lambda_min=lam.value, **info.as_dict())
+        if v is not None and not info.certified:
+            out["eigvec"] = from_dev_layout(v, self.r)
+        return out
 
     def escape(self, X, v, lambda_min, params: "EscapeParams | None" = None):
         """The rank staircase's escape with its line search on this handle (single agent, rank r + 1, Q set): X
@@ -849,6 +905,8 @@ _SIGS2 = [
      C.c_int),
     ("dpgo_graph_certify_ex", [C.c_void_p, C.c_int, _dp, C.c_int, C.c_int, C.c_int, C.c_double, _dp, _dp, _dp, _dp,
                                _dp, C.c_void_p], C.c_int),
+    ("dpgo_graph_certify_chol", [C.c_void_p, C.c_int, _dp, _dp, C.c_double, C.POINTER(CholCertParams), _dp, _dp, _dp,
+                                 C.POINTER(CholCertInfo)], C.c_int),
     ("dpgo_graph_escape", [C.c_void_p, C.c_int, _dp, _dp, C.c_int, C.c_double, C.POINTER(EscapeParams), _dp,
                            C.POINTER(EscapeInfo)], C.c_int),
     ("dpgo_graph_rank_reduce", [C.c_void_p, C.c_int, _dp, C.c_double, _ip, _dp, C.POINTER(RankInfo)], C.c_int),
@@ -1084,6 +1142,32 @@ class Graph:
             out["T_rounded"] = from_dev_layout(T, self.d)
         if V is not None:
             out["eigvec"] = V.reshape(-1, r).T if V.ndim == 1 else V  # r x (d+1) n
+        return out
+
+    def certify_chol(self, X, r, eta, w=None, want_vector=True, **params):
+        """The certificate by factorisation for the whole graph (dpgo_graph_certify_chol): X as certify() takes it, w
+        per-edge weights in the graph's order (None: ones; Rbcd.get_weights() certifies the problem a robust run
+        solved).  dict(lambda_min, f_relax, pd, certified, factorisations, sigma_lo, sigma_hi, invit_iters, residual,
+        factor_ms, panel_doubles[, eigvec r x (d+1) n]).  Certified (S(X) + eta I positive definite): lambda_min =
+        -eta and no eigvec.  params: the fields of dpgo_chol_cert_params."""
+        X = np.asarray(X, dtype=np.float64)
+        flat = np.ascontiguousarray(X.T).ravel() if X.ndim == 2 else np.ascontiguousarray(X).ravel()
+        if flat.size != r * (self.d + 1) * self.n:
+            raise DPGOHipError("X has the wrong size")
+        wp = None
+        if w is not None:
+            w, wp = _f64(w)
+            if w.size != self.m:
+                raise DPGOHipError("w must have one weight per edge")
+        lam, fx, info = C.c_double(), C.c_double(), CholCertInfo()
+        V = np.empty(flat.size) if want_vector else None
+        _check(lib().dpgo_graph_certify_chol(self.h, int(r), flat.ctypes.data_as(_dp), wp, float(eta),
+                                             C.byref(chol_cert_params(**params)), C.byref(lam),
+                                             V.ctypes.data_as(_dp) if V is not None else None, C.byref(fx),
+                                             C.byref(info)))
+        out = dict(lambda_min=lam.value, f_relax=fx.value, pd=bool(info.certified), **info.as_dict())
+        if V is not None and not info.certified:
+            out["eigvec"] = V.reshape(-1, r).T  # r x (d+1) n
         return out
 
     def escape(self, X, r, vec, lambda_min, params: "EscapeParams | None" = None):

@@ -17,7 +17,7 @@ class StaircaseError(RuntimeError):
 
 
 def solve(graph: "H.Graph", agent_of_pose, agent_rank, X0, r0, params: "H.RbcdParams | None" = None, r_max=8,
-          eta=1e-6, grad_tol=1e-6, max_steps=10000, cert=None, escape=None, reduce_tol=None):
+          eta=1e-6, grad_tol=1e-6, max_steps=10000, cert=None, escape=None, reduce_tol=None, certifier="lanczos"):
     """Solve the pose graph from X0 (r0 x (d+1) n matrix, or its flat column-major buffer), raising the rank until
     the certificate holds.
 
@@ -35,7 +35,15 @@ def solve(graph: "H.Graph", agent_of_pose, agent_rank, X0, r0, params: "H.RbcdPa
     grad_tol or max_steps) and Graph.certify decides at rank k.  The rank-k X is returned when it certifies
     (lambda_min >= -eta), the certified rank-r X otherwise; either way levels gains one entry for rank k that also
     carries reduced_from = r, dropped (the Gram eigenvalues cut off), w (the Gram's spectrum) and certified.  When
-    the numerical rank is r itself nothing is added and the return is that of reduce_tol=None."""
+    the numerical rank is r itself nothing is added and the return is that of reduce_tol=None.
+
+    certifier="chol": every certificate is Graph.certify_chol(X, r, eta) instead (the Cholesky test of S(X) + eta I,
+    and on failure a bracket and inverse iteration for lambda_min and its vector); `cert` then holds
+    dpgo_chol_cert_params fields.  A certified level records lambda_min = -eta (the bound the test proves) and
+    pd = True, an uncertified one pd = False; each carries factorisations and invit_iters.  A level whose whole-graph
+    factor is refused for its size is certified by Graph.certify with its defaults and records fallback = True."""
+    if certifier not in ("lanczos", "chol"):
+        raise StaircaseError(f"unknown certifier {certifier!r}")
     ar = np.asarray(agent_rank, dtype=np.int32)
     if np.any(ar != 0):
         raise StaircaseError("staircase.solve runs on one rank: agent_rank must be all zero")
@@ -71,12 +79,24 @@ def solve(graph: "H.Graph", agent_of_pose, agent_rank, X0, r0, params: "H.RbcdPa
             e.close()
         return X, steps, f, float(np.sqrt(gsq.sum())), p
 
+    def certify(X, r):
+        """The level's certificate: (dict with lambda_min and, when it is negative, eigvec; extra level fields)."""
+        if certifier == "lanczos":
+            return graph.certify(X, r, want_vector=True, **cert), {}
+        try:
+            c = graph.certify_chol(X, r, eta, **cert)
+        except H.DPGOHipError as e:
+            if "GiB" not in str(e) and "memory" not in str(e).lower():
+                raise
+            return graph.certify(X, r, want_vector=True), dict(fallback=True)
+        return c, dict(pd=c["pd"], fallback=False, factorisations=c["factorisations"], invit_iters=c["invit_iters"])
+
     while True:
         X, steps, f, gradnorm, p = run_level(r, X)
-        c = graph.certify(X, r, want_vector=True, **cert)
+        c, extra = certify(X, r)
         lam = c["lambda_min"]
-        levels.append(dict(r=r, steps=steps, f=f, gradnorm=gradnorm, lambda_min=lam, alpha=0.0, trials=0))
-        if lam >= -eta:
+        levels.append(dict(r=r, steps=steps, f=f, gradnorm=gradnorm, lambda_min=lam, alpha=0.0, trials=0, **extra))
+        if extra.get("pd", lam >= -eta):  # the factorisation's own decision where it made one
             break
         if r >= r_max:
             raise StaircaseError(f"rank {r} reached uncertified: lambda_min = {lam:.3e}")
@@ -94,7 +114,8 @@ def solve(graph: "H.Graph", agent_of_pose, agent_rank, X0, r0, params: "H.RbcdPa
     if k == r:
         return X, r, levels
     Xk, steps, f, gradnorm, _ = run_level(k, Xk)
-    lam = graph.certify(Xk, k, **cert)["lambda_min"]
+    c, extra = (graph.certify(Xk, k, **cert), {}) if certifier == "lanczos" else certify(Xk, k)
+    lam = c["lambda_min"]
     levels.append(dict(r=k, steps=steps, f=f, gradnorm=gradnorm, lambda_min=lam, alpha=0.0, trials=0, reduced_from=r,
-                       dropped=info["dropped"], w=info["w"], certified=bool(lam >= -eta)))
-    return (Xk, k, levels) if lam >= -eta else (X, r, levels)
+                       dropped=info["dropped"], w=info["w"], certified=bool(extra.get("pd", lam >= -eta)), **extra))
+    return (Xk, k, levels) if levels[-1]["certified"] else (X, r, levels)

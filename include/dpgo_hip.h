@@ -282,6 +282,44 @@ typedef struct {
 int dpgo_hip_certify_ex(dpgo_hip_problem h, const double* X, int max_iters, int basis_max, int flags, double tol,
                         double* lambda_min, double* eigvec, dpgo_cert_info* info);
 
+/* ---- certification by factorisation (SE-Sync's fast verification; build-defined: pinned against dense Cholesky
+ * and eigenvalues of the explicitly formed matrix) ---------------------------------------------------
+ * S(X) = Q - Lambda(X) has Q's block pattern, so S(X) + sigma I goes through the exact preconditioner's
+ * supernodal Cholesky with other diagonal blocks and another shift.  *pd = 1 iff no pivot of the factorisation of
+ * S(X) + sigma I failed d > 0, which means lambda_min(S(X)) > -sigma up to the factorisation's backward error.
+ * The numeric factorisation always runs on the device, on a factor state of its own: a handle that also uses
+ * DPGO_PRECON_EXACT keeps its preconditioner's factor and counters as they were.  Single-agent handles with an
+ * edge-stream Q (DPGO_HIP_EINVAL otherwise, and for a non-finite sigma); the exact preconditioner's size refusals
+ * (the 24 GiB panel cap, host memory) surface unchanged. */
+int dpgo_hip_certify_chol(dpgo_hip_problem h, const double* X, double sigma, int* pd);
+typedef struct {
+  double ratio;            /* the bracket is bisected on log sigma until sigma_hi / sigma_lo <= ratio (1 + 1/16) */
+  int max_factorisations;  /* ... or this many factorisations were run (24) */
+  double tol;              /* inverse iteration stops at |v S - lambda v| <= tol * sigma_top (1e-8) */
+  int max_iters;           /* ... or after this many solves (200) */
+} dpgo_chol_cert_params;
+void dpgo_default_chol_cert_params(dpgo_chol_cert_params* p);
+typedef struct {
+  int certified;           /* 1: S(X) + eta I is positive definite, lambda_min > -eta; nothing else was computed */
+  int factorisations;      /* numeric factorisations of this call */
+  double sigma_lo;         /* S + sigma_lo I not positive definite, S + sigma_hi I positive definite:          */
+  double sigma_hi;         /* -sigma_hi < lambda_min <= -sigma_lo (certified: sigma_lo = sigma_hi = eta)       */
+  int invit_iters;         /* inverse iterations (solves with the factor at sigma_hi) */
+  double residual;         /* |v S - lambda v| of the returned pair */
+  double factor_ms;        /* device time of the last factorisation */
+  long long panel_doubles; /* doubles of the factor's stored panels */
+} dpgo_chol_cert_info;
+/* lambda_min(S(X)) by a bracket and shifted inverse iteration.  First the test at sigma = eta (> 0); positive
+ * definite: certified, *lambda_min = -eta (a strict lower bound), eigvec untouched.  Otherwise sigma_top =
+ * (1 + 1e-6) max_j |Lambda_j|_F + eta is confirmed positive definite (Q >= 0; DPGO_HIP_EDEVICE if it is not), the
+ * bracket [eta, sigma_top] is bisected on log sigma, every trial one numeric refactorisation, and inverse iteration
+ * v <- normalise(v (S + sigma_hi I)^-1) from a seeded start on row 0 of the lifted layout converges at the rate
+ * (lambda_min + sigma_hi) / (lambda_2 + sigma_hi).  *lambda_min: the Rayleigh quotient <v S, v> (an upper bound
+ * of lambda_min, as the Lanczos value); eigvec (host, r x (d+1) n, optional): the unit vector on row 0, rows 1..
+ * zero, as dpgo_hip_escape_direction takes it.  p NULL: the defaults.  Outputs are written only on success. */
+int dpgo_hip_certify_chol_ex(dpgo_hip_problem h, const double* X, double eta, const dpgo_chol_cert_params* p,
+                             double* lambda_min, double* eigvec, dpgo_chol_cert_info* info);
+
 /* ---- rank staircase (SE-Sync / DC2-PGO's Riemannian staircase; not in the reference: pinned against the
  * oracle's retract_qf and a numpy restatement) ------------------------------------------------------
  * When the certificate fails at a critical point X of rank r (lambda_min(S(X)) < 0 with eigenvector v, a

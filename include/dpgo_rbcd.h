@@ -138,6 +138,13 @@ int dpgo_graph_certify(dpgo_graph g, int r, const double* X, int max_iters, doub
 int dpgo_graph_certify_ex(dpgo_graph g, int r, const double* X, int max_iters, int basis_max, int flags, double tol,
                           double* lambda_min, double* f_relax, double* f_rounded, double* T_rounded, double* eigvec,
                           dpgo_cert_info* info);
+/* The certificate by factorisation (dpgo_hip_certify_chol_ex) on the whole graph's central edge-stream handle with
+ * the weights w (per edge in the graph's order; NULL: ones).  dpgo_rbcd_get_weights' array gives the certificate of
+ * the problem a robust run solved: S(X) is then the weighted Q's.  f_relax (optional) = f(X) with the same
+ * weights.  eigvec (optional, r x (d+1) n) as dpgo_graph_escape takes it, untouched when info->certified. */
+int dpgo_graph_certify_chol(dpgo_graph g, int r, const double* X, const double* w, double eta,
+                            const dpgo_chol_cert_params* p, double* lambda_min, double* eigvec, double* f_relax,
+                            dpgo_chol_cert_info* info);
 /* The rank staircase's step for the whole graph, next to dpgo_graph_certify_ex: when that returned lambda_min < 0
  * at a critical point X of rank r, X_out ((r+1) x (d+1) n, column-major) = dpgo_hip_escape on the central
  * unit-weight edge-stream handle at rank r + 1, along dpgo_hip_escape_direction of eigvec_or_v (vec_rows x (d+1) n,
