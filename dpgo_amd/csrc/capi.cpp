@@ -1788,9 +1788,13 @@ std::vector<double> tridiag_lowest_vector(const std::vector<double>& a, const st
   return x;
 }
 
+}  // namespace
+
+namespace dpgo {
+
 // Eigenpairs of the dense symmetric m x m matrix A (row-major): Householder reduction to tridiagonal form
 // (A = Q T Q^T, Q accumulated) and tridiag_eig on T; Z as tridiag_eig's (eigenvectors of A, then the
-// ascending eigenvalues).
+// ascending eigenvalues).  Shared with the block certificate (blockcert.cpp).
 void sym_eig(int m, std::vector<double> A, std::vector<double>& Z) {
   std::vector<double> Q(static_cast<size_t>(m) * m, 0.0), v(m), p(m), wv(m);
   for (int i = 0; i < m; ++i) Q[static_cast<size_t>(i) * m + i] = 1.0;
@@ -1844,7 +1848,7 @@ void sym_eig(int m, std::vector<double> A, std::vector<double>& Z) {
   std::copy(Zt.begin() + static_cast<long>(m) * m, Zt.end(), Z.begin() + static_cast<long>(m) * m);
 }
 
-}  // namespace
+}  // namespace dpgo
 
 extern "C" {
 

@@ -709,6 +709,27 @@ int dpgo_graph_certify_chol(dpgo_graph g, int r, const double* X, const double* 
   return DPGO_HIP_OK;
 }
 
+// The block certificate on the whole graph (build-defined): the same central handle and weights
+int dpgo_graph_certify_block(dpgo_graph g, int r, const double* X, const double* w, const dpgo_block_cert_params* p,
+                             double* lambda_min, double* eigvec, double* f_relax, dpgo_cert_info* info) {
+  if (!g || !X || !lambda_min || r < g->d) return fail(DPGO_HIP_EINVAL, "bad certification arguments");
+  const int d = g->d, n = g->n, m = static_cast<int>(g->p1.size());
+  dpgo_hip_problem h = nullptr;
+  DPGO_TRY(dpgo_hip_problem_create(n, d, r, &h));
+  struct Guard {
+    dpgo_hip_problem h;
+    ~Guard() { dpgo_hip_problem_destroy(h); }
+  } guard{h};
+  const std::vector<double> ones(w ? 0 : static_cast<size_t>(m), 1.0);
+  DPGO_TRY(dpgo_hip_set_Q_edges(h, 0, m, g->p1.data(), g->p2.data(), g->R.data(), g->t.data(), g->kappa.data(),
+                                g->tau.data(), w ? w : ones.data()));
+  double fx = 0.0;  // before the certificate, so an error leaves every output untouched
+  if (f_relax) DPGO_TRY(dpgo_hip_f(h, X, &fx));
+  DPGO_TRY(dpgo_hip_certify_block(h, X, p, lambda_min, eigvec, info));
+  if (f_relax) *f_relax = fx;
+  return DPGO_HIP_OK;
+}
+
 // The rank staircase's step on the whole graph (build-defined, next to dpgo_graph_certify_ex): the central
 // unit-weight edge-stream handle at rank r + 1, the direction from the certificate's Ritz matrix (or a plain
 // eigenvector, vec_rows = 1), and dpgo_hip_escape's line search on it.  X_out: (r + 1) x (d+1) n, column-major.

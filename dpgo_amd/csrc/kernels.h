@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+
 #include "chol_internal.h"
 #include "dpgo_device.h"
 
@@ -551,6 +553,53 @@ hipError_t launch_bj_inverse_diag(int b, int n, const QView& q, double shift, do
 // The certificate matrix's packed diagonal blocks: out_j = diag_j - [S_j 0; 0 0] per pose (diag: diag_width(d)
 // doubles per pose, S: the packed d x d sym(Y_j^T (XQ+G)_Y) an EVAL pass leaves).  out must not alias diag.
 hipError_t launch_cert_diag(int b, int n, const double* diag, const double* S, double* out, hipStream_t stream);
+
+// ---- Block certificate (build-defined): LOBPCG on the r rows of the lifted layout.  A
+// block is an r-row slice of that layout, entry (row i, column x) at p[x * ld + i] with ld = r (the locked block U:
+// r + 1 rows, zero-padded), nc = (d + 1) n columns.  Reductions: one partial per workgroup of a grid that depends on
+// nc alone, summed in a fixed order by a finishing launch; no atomics, so every result is a function of its inputs.
+constexpr int kBlkGramBlocks = 1024;  // workgroups of the Gram kernel at most (64 columns per step each)
+constexpr int kBlkVecBlocks = 1024;   // workgroups of the per-column kernels at most
+inline int blk_gram_grid(long nc) { return static_cast<int>(std::min<long>((nc + 63) / 64, kBlkGramBlocks)); }
+// doubles of `partial` the launches below need: the Gram of up to 3 r x (6 r + 1) products, r row norms
+inline long blk_partial_doubles(int r) { return static_cast<long>(kBlkGramBlocks) * 3 * r * (6 * r + 1); }
+struct BlkList {
+  const double* p[6];
+  int ld[6];  // r, or r + 1 for U
+  int n;      // blocks in use (<= 6, at most 6 r + 1 rows together)
+};
+// out[i * rows + j] = <row i, row j>: i over the rows of the first nleft blocks (<= 3 r), j over the rows of all of
+// them (rows = sum of ld), each block read once
+hipError_t launch_blk_gram(int r, long nc, const BlkList& L, int nleft, double* partial, double* out,
+                           hipStream_t stream);
+// out = SX - diag(theta) X (theta: r doubles on the device); norms[i] = |out_i|^2
+hipError_t launch_blk_residual(int r, long nc, const double* SX, const double* X, const double* theta, double* out,
+                               double* partial, double* norms, hipStream_t stream);
+// V <- V - coef U, U of ru rows (r or r + 1), coef r x ru at coef[i * ldc + j] on the device; partial and norms both
+// given: norms[i] = |V_i|^2 of the result, both null: none
+hipError_t launch_blk_project(int r, int ru, long nc, double* V, const double* U, const double* coef, int ldc,
+                              double* partial, double* norms, hipStream_t stream);
+// V <- T V (T r x r row-major on the device)
+hipError_t launch_blk_transform(int r, long nc, double* V, const double* T, hipStream_t stream);
+// x' = cx [x; w; p], p' = cp [x; w; p] and the same for (sx, sw, sp), in place (cx, cp: r x 3r row-major on the
+// device; cp's first r columns are not read); has_p == 0: p and sp are written only
+struct BlkCombine {
+  double* x;
+  const double* w;
+  double* p;
+  double* sx;
+  const double* sw;
+  double* sp;
+  const double* cx;
+  const double* cp;
+  int has_p;
+};
+hipError_t launch_blk_combine(int r, long nc, const BlkCombine& a, hipStream_t stream);
+// V_j <- V_j Minv_j per pose (n poses of r x b), Minv as launch_bj_inverse* leave it
+hipError_t launch_blk_precond(int r, int b, long n, double* V, const double* Minv, hipStream_t stream);
+// T (r x r row-major) orthonormalising the rows whose r x r Gram matrix is G (G[i * ldg + j]): row i of T is the
+// i-th largest eigenvalue's vector over the root of the eigenvalue, or zero when that is <= drop * the largest
+hipError_t launch_blk_orthcoef(int r, const double* G, int ldg, double drop, double* T, hipStream_t stream);
 
 // ---- Jacobi-PCG on SPD block-sparse systems with several right-hand sides (GPU chordal
 // initialisation, init.cpp).  Vectors are [row][bs][nr]: row p holds bs x nr doubles (column a of

@@ -6077,6 +6077,358 @@ hipError_t launch_bj_inverse(int b, int n, const QView& q, double shift, double*
   return hipGetLastError();
 }
 
+// ---- Block certificate (LOBPCG on the r rows of the lifted layout) ------------------------------
+// A block is an R-row slice of the lifted layout: entry (row i, column x) at p[x * ld + i], ld = R (the locked block
+// U: R + 1).  Every reduction leaves one partial per workgroup of a grid that depends on the column count alone and
+// is finished by k_blk_sum in a fixed order: no atomics, the same bits on every call.
+constexpr int kBlkChunk = 64;  // columns per LDS tile of k_blk_gram
+
+// partial[g][i * rows + j] = <row i, row j> over workgroup g's column chunks, i over the first left_rows rows of the
+// list's concatenated rows, j over all of them.  The chunk of every block is staged once in LDS (row stride
+// kBlkChunk + 1: the rows a wave reads at one column sit on distinct banks) and the products are split over the
+// threads, NACC per thread, so one launch reads each block once for all of them.
+template <int R>
+__global__ __launch_bounds__(kThreads) void k_blk_gram(long nc, BlkList L, int left_rows, int rows,
+                                                       double* __restrict__ partial) {
+  constexpr int kMaxRows = 6 * R + 1, NACC = (3 * R * kMaxRows + kThreads - 1) / kThreads;
+  __shared__ double s[kMaxRows][kBlkChunk + 1];
+  const int t = threadIdx.x, nout = left_rows * rows;
+  int oi[NACC], oj[NACC];
+  double acc[NACC];
+#pragma unroll
+  for (int q = 0; q < NACC; ++q) {
+    const int o = t + q * kThreads;
+    oi[q] = o < nout ? o / rows : 0;
+    oj[q] = o < nout ? o - oi[q] * rows : 0;
+    acc[q] = 0.0;
+  }
+  const long nchunks = (nc + kBlkChunk - 1) / kBlkChunk;
+  for (long ch = blockIdx.x; ch < nchunks; ch += gridDim.x) {
+    const long c0 = ch * kBlkChunk;
+    const int ncol = static_cast<int>(min(static_cast<long>(kBlkChunk), nc - c0));
+    int roff = 0;
+    for (int k = 0; k < L.n; ++k) {
+      const int ld = L.ld[k];
+      const double* __restrict__ p = L.p[k] + c0 * ld;
+      for (int e = t; e < kBlkChunk * ld; e += kThreads) {
+        const int col = e / ld, row = e - col * ld;
+        s[roff + row][col] = col < ncol ? p[e] : 0.0;
+      }
+      roff += ld;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < NACC; ++q) {
+      const double* a = s[oi[q]];
+      const double* b = s[oj[q]];
+      double v = acc[q];
+#pragma unroll 8
+      for (int c = 0; c < kBlkChunk; ++c) v = fma(a[c], b[c], v);
+      acc[q] = v;
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int q = 0; q < NACC; ++q) {
+    const int o = t + q * kThreads;
+    if (o < nout) partial[static_cast<long>(blockIdx.x) * nout + o] = acc[q];
+  }
+}
+
+// out[o] = partial[0][o] + partial[1][o] + ... in that order (one thread per entry, coalesced across entries)
+__global__ __launch_bounds__(kThreads) void k_blk_sum(int blocks, int nout, const double* __restrict__ partial,
+                                                      double* __restrict__ out) {
+  const int o = blockIdx.x * kThreads + threadIdx.x;
+  if (o >= nout) return;
+  double v = 0.0;
+  for (int g = 0; g < blocks; ++g) v += partial[static_cast<long>(g) * nout + o];
+  out[o] = v;
+}
+
+// the workgroup's per-row sums of nrm into part[block][R]; every thread of the workgroup calls it
+template <int R>
+__device__ __forceinline__ void blk_row_sums(const double (&nrm)[R], double* __restrict__ part) {
+  __shared__ double red[R][kThreads / 64];
+#pragma unroll
+  for (int i = 0; i < R; ++i) {
+    const double v = wave_sum(nrm[i]);
+    if ((threadIdx.x & 63) == 0) red[i][threadIdx.x >> 6] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < R)
+    part[static_cast<long>(blockIdx.x) * R + threadIdx.x] =
+        ((red[threadIdx.x][0] + red[threadIdx.x][1]) + red[threadIdx.x][2]) + red[threadIdx.x][3];
+}
+
+// out = SX - diag(theta) X, and the partials of |out_i|^2 per row
+template <int R>
+__global__ __launch_bounds__(kThreads) void k_blk_residual(long nc, const double* __restrict__ SX,
+                                                           const double* __restrict__ X,
+                                                           const double* __restrict__ theta, double* __restrict__ out,
+                                                           double* __restrict__ part) {
+  double nrm[R];
+#pragma unroll
+  for (int i = 0; i < R; ++i) nrm[i] = 0.0;
+  for (long x = static_cast<long>(blockIdx.x) * kThreads + threadIdx.x; x < nc;
+       x += static_cast<long>(gridDim.x) * kThreads) {
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+      const double v = fma(-theta[i], X[x * R + i], SX[x * R + i]);
+      out[x * R + i] = v;
+      nrm[i] = fma(v, v, nrm[i]);
+    }
+  }
+  blk_row_sums<R>(nrm, part);
+}
+
+// V <- V - coef U (coef R x RU at coef[i * ldc + j], left on the device by the cross Gram), and optionally the
+// partials of the result's |V_i|^2
+template <int R, int RU>
+__global__ __launch_bounds__(kThreads) void k_blk_project(long nc, double* __restrict__ V, const double* __restrict__ U,
+                                                          const double* __restrict__ coef, int ldc,
+                                                          double* __restrict__ part) {
+  double nrm[R];
+#pragma unroll
+  for (int i = 0; i < R; ++i) nrm[i] = 0.0;
+  for (long x = static_cast<long>(blockIdx.x) * kThreads + threadIdx.x; x < nc;
+       x += static_cast<long>(gridDim.x) * kThreads) {
+    double u[RU];
+#pragma unroll
+    for (int j = 0; j < RU; ++j) u[j] = U[x * RU + j];
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+      double v = V[x * R + i];
+#pragma unroll
+      for (int j = 0; j < RU; ++j) v = fma(-coef[i * ldc + j], u[j], v);
+      V[x * R + i] = v;
+      nrm[i] = fma(v, v, nrm[i]);
+    }
+  }
+  if (part != nullptr) blk_row_sums<R>(nrm, part);  // uniform over the workgroup
+}
+
+// V <- T V per column (T R x R row-major on the device)
+template <int R>
+__global__ __launch_bounds__(kThreads) void k_blk_transform(long nc, double* __restrict__ V,
+                                                            const double* __restrict__ T) {
+  for (long x = static_cast<long>(blockIdx.x) * kThreads + threadIdx.x; x < nc;
+       x += static_cast<long>(gridDim.x) * kThreads) {
+    double v[R], o[R];
+#pragma unroll
+    for (int j = 0; j < R; ++j) v[j] = V[x * R + j];
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+      double a = 0.0;
+#pragma unroll
+      for (int j = 0; j < R; ++j) a = fma(T[i * R + j], v[j], a);
+      o[i] = a;
+    }
+#pragma unroll
+    for (int i = 0; i < R; ++i) V[x * R + i] = o[i];
+  }
+}
+
+// The Rayleigh-Ritz update, in place per column: x' = cx [x; w; p], p' = cp [x; w; p] (R x 3R row-major tiles on the
+// device; cp's x part is zero and not read), for the vector blocks (blockIdx.y 0) and their operator images (1) in
+// one launch.  has_p == 0: the p block does not exist yet and is not read.
+template <int R>
+__global__ __launch_bounds__(kThreads) void k_blk_combine(long nc, BlkCombine a) {
+  double* __restrict__ X = blockIdx.y == 0 ? a.x : a.sx;
+  const double* __restrict__ W = blockIdx.y == 0 ? a.w : a.sw;
+  double* __restrict__ P = blockIdx.y == 0 ? a.p : a.sp;
+  const double* __restrict__ cx = a.cx;
+  const double* __restrict__ cp = a.cp;
+  const bool has_p = a.has_p != 0;
+  for (long x = static_cast<long>(blockIdx.x) * kThreads + threadIdx.x; x < nc;
+       x += static_cast<long>(gridDim.x) * kThreads) {
+    double z[3 * R];
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+      z[j] = X[x * R + j];
+      z[R + j] = W[x * R + j];
+      z[2 * R + j] = has_p ? P[x * R + j] : 0.0;
+    }
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+      double xo = 0.0, po = 0.0;
+#pragma unroll
+      for (int j = 0; j < 3 * R; ++j) xo = fma(cx[i * 3 * R + j], z[j], xo);
+#pragma unroll
+      for (int j = R; j < 3 * R; ++j) po = fma(cp[i * 3 * R + j], z[j], po);
+      X[x * R + i] = xo;
+      P[x * R + i] = po;
+    }
+  }
+}
+
+// V_j <- V_j Minv_j per pose (the block-Jacobi inverses as launch_bj_inverse* leave them), one thread per pose
+template <int R, int B>
+__global__ __launch_bounds__(kThreads) void k_blk_precond(long n, double* __restrict__ V,
+                                                          const double* __restrict__ Minv) {
+  const long j = static_cast<long>(blockIdx.x) * kThreads + threadIdx.x;
+  if (j >= n) return;
+  double M[B][B], v[R][B];
+#pragma unroll
+  for (int u = 0; u < B; ++u)
+#pragma unroll
+    for (int w = 0; w < B; ++w) M[u][w] = Minv[j * diag_width(B - 1) + minv_index<B>(u, w)];
+#pragma unroll
+  for (int k = 0; k < B; ++k)
+#pragma unroll
+    for (int a = 0; a < R; ++a) v[a][k] = V[(j * B + k) * R + a];
+#pragma unroll
+  for (int k = 0; k < B; ++k)
+#pragma unroll
+    for (int a = 0; a < R; ++a) {
+      double z = 0.0;
+#pragma unroll
+      for (int u = 0; u < B; ++u) z = fma(v[a][u], M[u][k], z);
+      V[(j * B + k) * R + a] = z;
+    }
+}
+
+// T (R x R row-major) with T G T^T = I on the kept directions of the R x R Gram matrix G (G[i * ldg + j],
+// symmetrised here): cyclic Jacobi by one thread, rows of T by descending eigenvalue, T_i = z_i / sqrt(e_i); an
+// eigenvalue at or below drop * the largest gives a zero row (and so does anything that is not a number).
+template <int R>
+__global__ __launch_bounds__(64) void k_blk_orthcoef(const double* __restrict__ G, int ldg, double drop,
+                                                     double* __restrict__ T) {
+  __shared__ double a[R][R], v[R][R], e[R];
+  __shared__ int ord[R];
+  if (threadIdx.x != 0) return;
+  for (int i = 0; i < R; ++i)
+    for (int j = 0; j < R; ++j) {
+      a[i][j] = 0.5 * (G[i * ldg + j] + G[j * ldg + i]);
+      v[i][j] = i == j ? 1.0 : 0.0;
+    }
+  for (int sweep = 0; sweep < 30; ++sweep) {
+    double off = 0.0, dia = 0.0;
+    for (int i = 0; i < R; ++i)
+      for (int j = 0; j < R; ++j) (i == j ? dia : off) += a[i][j] * a[i][j];
+    if (!(off > 1e-34 * dia)) break;
+    for (int p = 0; p + 1 < R; ++p)
+      for (int q = p + 1; q < R; ++q) {
+        const double apq = a[p][q];
+        if (apq == 0.0) continue;
+        const double tau = (a[q][q] - a[p][p]) / (2.0 * apq);
+        const double tt = (tau >= 0.0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
+        const double c = 1.0 / sqrt(1.0 + tt * tt), sn = tt * c;
+        for (int k = 0; k < R; ++k) {
+          const double akp = a[k][p], akq = a[k][q];
+          a[k][p] = c * akp - sn * akq;
+          a[k][q] = sn * akp + c * akq;
+        }
+        for (int k = 0; k < R; ++k) {
+          const double apk = a[p][k], aqk = a[q][k];
+          a[p][k] = c * apk - sn * aqk;
+          a[q][k] = sn * apk + c * aqk;
+        }
+        for (int k = 0; k < R; ++k) {
+          const double vkp = v[k][p], vkq = v[k][q];
+          v[k][p] = c * vkp - sn * vkq;
+          v[k][q] = sn * vkp + c * vkq;
+        }
+      }
+  }
+  for (int i = 0; i < R; ++i) {
+    e[i] = a[i][i];
+    ord[i] = i;
+  }
+  for (int i = 0; i + 1 < R; ++i)  // descending, ties by index
+    for (int j = i + 1; j < R; ++j)
+      if (e[ord[j]] > e[ord[i]]) {
+        const int tmp = ord[i];
+        ord[i] = ord[j];
+        ord[j] = tmp;
+      }
+  const double emax = e[ord[0]];
+  for (int i = 0; i < R; ++i) {
+    const int c = ord[i];
+    const bool keep = emax > 0.0 && e[c] > drop * emax;
+    const double sc = keep ? 1.0 / sqrt(e[c]) : 0.0;
+    for (int j = 0; j < R; ++j) T[i * R + j] = keep ? v[j][c] * sc : 0.0;
+  }
+}
+
+#define DPGO_DISPATCH_R(R_, CALL)                     \
+  switch (R_) {                                       \
+    case 2: { constexpr int R = 2; CALL; break; }     \
+    case 3: { constexpr int R = 3; CALL; break; }     \
+    case 4: { constexpr int R = 4; CALL; break; }     \
+    case 5: { constexpr int R = 5; CALL; break; }     \
+    case 6: { constexpr int R = 6; CALL; break; }     \
+    case 7: { constexpr int R = 7; CALL; break; }     \
+    case 8: { constexpr int R = 8; CALL; break; }     \
+    default: return hipErrorInvalidValue;             \
+  }
+
+static int blk_vec_grid(long nc) {
+  return static_cast<int>(std::min<long>((nc + kThreads - 1) / kThreads, kBlkVecBlocks));
+}
+
+hipError_t launch_blk_gram(int r, long nc, const BlkList& L, int nleft, double* partial, double* out,
+                           hipStream_t stream) {
+  if (nc <= 0 || L.n < 1 || L.n > 6 || nleft < 1 || nleft > L.n || nleft > 3) return hipErrorInvalidValue;
+  int rows = 0, left_rows = 0;
+  for (int k = 0; k < L.n; ++k) {
+    if (L.p[k] == nullptr || (L.ld[k] != r && L.ld[k] != r + 1)) return hipErrorInvalidValue;
+    rows += L.ld[k];
+    if (k < nleft) left_rows += L.ld[k];
+  }
+  if (rows > 6 * r + 1 || left_rows > 3 * r) return hipErrorInvalidValue;
+  const int grid = blk_gram_grid(nc), nout = left_rows * rows;
+  DPGO_DISPATCH_R(r, (k_blk_gram<R><<<grid, kThreads, 0, stream>>>(nc, L, left_rows, rows, partial)));
+  k_blk_sum<<<(nout + kThreads - 1) / kThreads, kThreads, 0, stream>>>(grid, nout, partial, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_blk_residual(int r, long nc, const double* SX, const double* X, const double* theta, double* out,
+                               double* partial, double* norms, hipStream_t stream) {
+  if (nc <= 0) return hipErrorInvalidValue;
+  const int grid = blk_vec_grid(nc);
+  DPGO_DISPATCH_R(r, (k_blk_residual<R><<<grid, kThreads, 0, stream>>>(nc, SX, X, theta, out, partial)));
+  k_blk_sum<<<1, kThreads, 0, stream>>>(grid, r, partial, norms);
+  return hipGetLastError();
+}
+
+hipError_t launch_blk_project(int r, int ru, long nc, double* V, const double* U, const double* coef, int ldc,
+                              double* partial, double* norms, hipStream_t stream) {
+  if (nc <= 0 || (ru != r && ru != r + 1) || (partial == nullptr) != (norms == nullptr)) return hipErrorInvalidValue;
+  const int grid = blk_vec_grid(nc);
+  if (ru == r) {
+    DPGO_DISPATCH_R(r, (k_blk_project<R, R><<<grid, kThreads, 0, stream>>>(nc, V, U, coef, ldc, partial)));
+  } else {
+    DPGO_DISPATCH_R(r, (k_blk_project<R, R + 1><<<grid, kThreads, 0, stream>>>(nc, V, U, coef, ldc, partial)));
+  }
+  if (partial != nullptr) k_blk_sum<<<1, kThreads, 0, stream>>>(grid, r, partial, norms);
+  return hipGetLastError();
+}
+
+hipError_t launch_blk_transform(int r, long nc, double* V, const double* T, hipStream_t stream) {
+  if (nc <= 0) return hipErrorInvalidValue;
+  DPGO_DISPATCH_R(r, (k_blk_transform<R><<<blk_vec_grid(nc), kThreads, 0, stream>>>(nc, V, T)));
+  return hipGetLastError();
+}
+
+hipError_t launch_blk_combine(int r, long nc, const BlkCombine& a, hipStream_t stream) {
+  if (nc <= 0) return hipErrorInvalidValue;
+  const dim3 grid(blk_vec_grid(nc), 2);
+  DPGO_DISPATCH_R(r, (k_blk_combine<R><<<grid, kThreads, 0, stream>>>(nc, a)));
+  return hipGetLastError();
+}
+
+hipError_t launch_blk_precond(int r, int b, long n, double* V, const double* Minv, hipStream_t stream) {
+  if (n <= 0) return hipErrorInvalidValue;
+  const int grid = static_cast<int>((n + kThreads - 1) / kThreads);
+  DPGO_DISPATCH(r, b, (k_blk_precond<R, B><<<grid, kThreads, 0, stream>>>(n, V, Minv)));
+  return hipGetLastError();
+}
+
+hipError_t launch_blk_orthcoef(int r, const double* G, int ldg, double drop, double* T, hipStream_t stream) {
+  DPGO_DISPATCH_R(r, (k_blk_orthcoef<R><<<1, 64, 0, stream>>>(G, ldg, drop, T)));
+  return hipGetLastError();
+}
+
 #endif  // !DPGO_SPMM_TU
 
 }  // namespace dpgo

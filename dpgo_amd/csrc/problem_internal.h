@@ -377,6 +377,10 @@ struct ScopedEvents {
 // launches of a standalone kernel benchmark that run before its timed window
 constexpr int kBenchWarmup = 3;
 
+// Eigenpairs of the dense symmetric m x m matrix A (row-major), capi.cpp: Z = the eigenvectors (vector c at
+// Z[c * m ..]) followed by the m ascending eigenvalues
+void sym_eig(int m, std::vector<double> A, std::vector<double>& Z);
+
 // exact.cpp: the exact preconditioner.  sync_chol brings the factor up to date with Q (symbolic build + upload on a
 // new pattern, the numeric factorisation alone after a reweighting); exact_precond applies it:
 // z = P_X(in (Q + 0.1 I)^-1) per agent, then projection + partials <z, rref>, |rref|^2 (pass rref = in).

@@ -67,6 +67,12 @@ class CholCertParams(C.Structure):
     _fields_ = [("ratio", C.c_double), ("max_factorisations", C.c_int), ("tol", C.c_double), ("max_iters", C.c_int)]
 
 
+class BlockCertParams(C.Structure):
+    """dpgo_block_cert_params (include/dpgo_hip.h)."""
+    _fields_ = [("max_iters", C.c_int), ("tol", C.c_double), ("flags", C.c_int), ("precon", C.c_int),
+                ("refresh", C.c_int)]
+
+
 class CholCertInfo(C.Structure):
     """dpgo_chol_cert_info (include/dpgo_hip.h)."""
     _fields_ = [("certified", C.c_int), ("factorisations", C.c_int), ("sigma_lo", C.c_double),
@@ -170,6 +176,8 @@ _SIGS = [
     ("dpgo_hip_certify_chol", [C.c_void_p, _dp, C.c_double, _ip], C.c_int),
     ("dpgo_hip_certify_chol_ex", [C.c_void_p, _dp, C.c_double, C.POINTER(CholCertParams), _dp, _dp,
                                   C.POINTER(CholCertInfo)], C.c_int),
+    ("dpgo_default_block_cert_params", [C.POINTER(BlockCertParams)], None),
+    ("dpgo_hip_certify_block", [C.c_void_p, _dp, C.POINTER(BlockCertParams), _dp, _dp, C.c_void_p], C.c_int),
     ("dpgo_hip_bench_hvp", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, _dp], C.c_int),
     ("dpgo_hip_stats", [C.c_void_p, _ip], C.c_int),
     ("dpgo_hip_set_trace", [C.c_void_p, C.c_int], C.c_int),
@@ -228,6 +236,17 @@ def chol_cert_params(**kw) -> CholCertParams:
     lib().dpgo_default_chol_cert_params(C.byref(p))
     for k, v in kw.items():
         if k not in dict(CholCertParams._fields_):
+            raise TypeError(f"unknown certificate parameter {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def block_cert_params(**kw) -> BlockCertParams:
+    """dpgo_default_block_cert_params with the given fields (max_iters, tol, flags, precon, refresh) replaced."""
+    p = BlockCertParams()
+    lib().dpgo_default_block_cert_params(C.byref(p))
+    for k, v in kw.items():
+        if k not in dict(BlockCertParams._fields_):
             raise TypeError(f"unknown certificate parameter {k!r}")
         setattr(p, k, v)
     return p
@@ -510,6 +529,20 @@ class Problem:
                                               C.byref(info)))
         out = dict(lambda_min=lam.value, **info.as_dict())
         if v is not None and not info.certified:
+            out["eigvec"] = from_dev_layout(v, self.r)
+        return out
+
+    def certify_block(self, X, want_vector=True, **params):
+        """The block certificate (dpgo_hip_certify_block: LOBPCG on the r lifted rows, any Q format and weights, any
+        size): dict(lambda_min, lower_bound and the other dpgo_cert_info fields[, eigvec r x (d+1) n: the unit vector
+        on row 0]).  params: the fields of dpgo_block_cert_params."""
+        x, xp = self._in(X)
+        lam, info = C.c_double(), CertInfo()
+        v = np.empty(self.vec_len) if want_vector else None
+        _check(lib().dpgo_hip_certify_block(self.h, xp, C.byref(block_cert_params(**params)), C.byref(lam),
+                                            v.ctypes.data_as(_dp) if v is not None else None, C.byref(info)))
+        out = dict(lambda_min=lam.value, **info.as_dict())
+        if v is not None:
             out["eigvec"] = from_dev_layout(v, self.r)
         return out
 
@@ -907,6 +940,8 @@ _SIGS2 = [
                                _dp, C.c_void_p], C.c_int),
     ("dpgo_graph_certify_chol", [C.c_void_p, C.c_int, _dp, _dp, C.c_double, C.POINTER(CholCertParams), _dp, _dp, _dp,
                                  C.POINTER(CholCertInfo)], C.c_int),
+    ("dpgo_graph_certify_block", [C.c_void_p, C.c_int, _dp, _dp, C.POINTER(BlockCertParams), _dp, _dp, _dp,
+                                  C.POINTER(CertInfo)], C.c_int),
     ("dpgo_graph_escape", [C.c_void_p, C.c_int, _dp, _dp, C.c_int, C.c_double, C.POINTER(EscapeParams), _dp,
                            C.POINTER(EscapeInfo)], C.c_int),
     ("dpgo_graph_rank_reduce", [C.c_void_p, C.c_int, _dp, C.c_double, _ip, _dp, C.POINTER(RankInfo)], C.c_int),
@@ -1167,6 +1202,31 @@ class Graph:
                                              C.byref(info)))
         out = dict(lambda_min=lam.value, f_relax=fx.value, pd=bool(info.certified), **info.as_dict())
         if V is not None and not info.certified:
+            out["eigvec"] = V.reshape(-1, r).T  # r x (d+1) n
+        return out
+
+    def certify_block(self, X, r, w=None, want_vector=True, **params):
+        """The block certificate for the whole graph (dpgo_graph_certify_block): X as certify() takes it, w per-edge
+        weights in the graph's order (None: ones; Rbcd.get_weights() certifies the problem a robust run solved), any
+        graph size.  dict(lambda_min, lower_bound, f_relax and the other dpgo_cert_info fields[, eigvec r x (d+1) n]).
+        params: the fields of dpgo_block_cert_params."""
+        X = np.asarray(X, dtype=np.float64)
+        flat = np.ascontiguousarray(X.T).ravel() if X.ndim == 2 else np.ascontiguousarray(X).ravel()
+        if flat.size != r * (self.d + 1) * self.n:
+            raise DPGOHipError("X has the wrong size")
+        wp = None
+        if w is not None:
+            w, wp = _f64(w)
+            if w.size != self.m:
+                raise DPGOHipError("w must have one weight per edge")
+        lam, fx, info = C.c_double(), C.c_double(), CertInfo()
+        V = np.empty(flat.size) if want_vector else None
+        _check(lib().dpgo_graph_certify_block(self.h, int(r), flat.ctypes.data_as(_dp), wp,
+                                              C.byref(block_cert_params(**params)), C.byref(lam),
+                                              V.ctypes.data_as(_dp) if V is not None else None, C.byref(fx),
+                                              C.byref(info)))
+        out = dict(lambda_min=lam.value, f_relax=fx.value, **info.as_dict())
+        if V is not None:
             out["eigvec"] = V.reshape(-1, r).T  # r x (d+1) n
         return out
 

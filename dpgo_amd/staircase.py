@@ -41,8 +41,14 @@ def solve(graph: "H.Graph", agent_of_pose, agent_rank, X0, r0, params: "H.RbcdPa
     and on failure a bracket and inverse iteration for lambda_min and its vector); `cert` then holds
     dpgo_chol_cert_params fields.  A certified level records lambda_min = -eta (the bound the test proves) and
     pd = True, an uncertified one pd = False; each carries factorisations and invit_iters.  A level whose whole-graph
-    factor is refused for its size is certified by Graph.certify with its defaults and records fallback = True."""
-    if certifier not in ("lanczos", "chol"):
+    factor is refused for its size is certified by Graph.certify with its defaults and records fallback = True.
+
+    certifier="lobpcg": every certificate is Graph.certify_block(X, r) (LOBPCG on the r lifted rows, any graph size);
+    `cert` then holds dpgo_block_cert_params fields.  A level is certified when the certificate's lower_bound >= -eta
+    (the bound, not the Ritz value, which only bounds lambda_min from above) and records lower_bound, bound_ok and
+    iters (operator passes); an uncertified level escapes along the certificate's vector.  A level whose bound fails
+    while its lambda_min is not negative (an unconverged certificate) raises StaircaseError."""
+    if certifier not in ("lanczos", "chol", "lobpcg"):
         raise StaircaseError(f"unknown certifier {certifier!r}")
     ar = np.asarray(agent_rank, dtype=np.int32)
     if np.any(ar != 0):
@@ -83,6 +89,9 @@ def solve(graph: "H.Graph", agent_of_pose, agent_rank, X0, r0, params: "H.RbcdPa
         """The level's certificate: (dict with lambda_min and, when it is negative, eigvec; extra level fields)."""
         if certifier == "lanczos":
             return graph.certify(X, r, want_vector=True, **cert), {}
+        if certifier == "lobpcg":
+            c = graph.certify_block(X, r, **cert)
+            return c, dict(lower_bound=c["lower_bound"], bound_ok=bool(c["lower_bound"] >= -eta), iters=c["iters"])
         try:
             c = graph.certify_chol(X, r, eta, **cert)
         except H.DPGOHipError as e:
@@ -96,8 +105,10 @@ def solve(graph: "H.Graph", agent_of_pose, agent_rank, X0, r0, params: "H.RbcdPa
         c, extra = certify(X, r)
         lam = c["lambda_min"]
         levels.append(dict(r=r, steps=steps, f=f, gradnorm=gradnorm, lambda_min=lam, alpha=0.0, trials=0, **extra))
-        if extra.get("pd", lam >= -eta):  # the factorisation's own decision where it made one
+        if extra.get("pd", extra.get("bound_ok", lam >= -eta)):  # the certifier's own decision where it made one
             break
+        if not lam < 0.0:
+            raise StaircaseError(f"rank {r} undecided: lower_bound = {extra.get('lower_bound')}, lambda_min = {lam:.3e}")
         if r >= r_max:
             raise StaircaseError(f"rank {r} reached uncertified: lambda_min = {lam:.3e}")
         ep = H.escape_params(min_gradnorm=p.tolerance)
@@ -117,5 +128,6 @@ def solve(graph: "H.Graph", agent_of_pose, agent_rank, X0, r0, params: "H.RbcdPa
     c, extra = (graph.certify(Xk, k, **cert), {}) if certifier == "lanczos" else certify(Xk, k)
     lam = c["lambda_min"]
     levels.append(dict(r=k, steps=steps, f=f, gradnorm=gradnorm, lambda_min=lam, alpha=0.0, trials=0, reduced_from=r,
-                       dropped=info["dropped"], w=info["w"], certified=bool(extra.get("pd", lam >= -eta)), **extra))
+                       dropped=info["dropped"], w=info["w"],
+                       certified=bool(extra.get("pd", extra.get("bound_ok", lam >= -eta))), **extra))
     return (Xk, k, levels) if levels[-1]["certified"] else (X, r, levels)

@@ -320,6 +320,33 @@ typedef struct {
 int dpgo_hip_certify_chol_ex(dpgo_hip_problem h, const double* X, double eta, const dpgo_chol_cert_params* p,
                              double* lambda_min, double* eigvec, dpgo_chol_cert_info* info);
 
+/* ---- block certificate (LOBPCG on the r rows of the lifted layout; build-defined: pinned against the eigenvalues
+ * of the explicitly formed matrix and a numpy restatement, tests/_lobpcg.py) --------------------------
+ * The operator V -> V S(X) acts on every row of the lifted r x (d+1) n layout in one launch, so the r rows serve as
+ * r start vectors per operator pass: locally optimal block preconditioned CG on the iterate X_b, the residual block
+ * W and the direction block P (six r-row blocks in all: the memory does not grow with the iteration count), one
+ * Rayleigh-Ritz of at most 3r x 3r per iteration on the host and one wait per iteration.  Any Q format, any
+ * weights (the handle's Q as it stands), no size refusal.  flags DPGO_CERT_SEED_X locks the block U of
+ * dpgo_hip_certify_ex (X's principal row directions and the translation gauge) and the iteration runs on its
+ * complement; info has dpgo_hip_certify_ex's meaning, with iters = operator passes (the start, one per iteration,
+ * one per refresh, the final residual's and those of U's block), restarts = iterations that ran without P because
+ * [X_b; W; P] had lost its conditioning, ritz = the block's r lowest values.  It stops when the lowest row's
+ * residual (off U) <= tol * the largest |Ritz value| seen, or after max_iters iterations.  precon = 1: W = R Minv per
+ * pose with the handle's block-Jacobi inverse of Q + 0.1 I (fewer iterations at a critical point, more at a
+ * random one).  eigvec (host, r x (d+1) n, optional): the unit vector on row 0, rows 1.. zero, as
+ * dpgo_hip_escape_direction takes it.  p NULL: the defaults.  DPGO_HIP_EINVAL, outputs untouched: a batched handle,
+ * 3 r > (d+1) n - seeds, max_iters < 1, a non-finite tol, an unknown precon or flag, refresh < 0. */
+typedef struct {
+  int max_iters; /* iterations at most (2000) */
+  double tol;    /* relative residual of the lowest pair (1e-8) */
+  int flags;     /* DPGO_CERT_SEED_X (the default) or 0 */
+  int precon;    /* 0 none (the default), 1 the handle's block-Jacobi inverse */
+  int refresh;   /* every this many iterations X_b is re-projected, re-orthonormalised and S X_b recomputed (50; 0 never) */
+} dpgo_block_cert_params;
+void dpgo_default_block_cert_params(dpgo_block_cert_params* p);
+int dpgo_hip_certify_block(dpgo_hip_problem h, const double* X, const dpgo_block_cert_params* p, double* lambda_min,
+                           double* eigvec, dpgo_cert_info* info);
+
 /* ---- rank staircase (SE-Sync / DC2-PGO's Riemannian staircase; not in the reference: pinned against the
  * oracle's retract_qf and a numpy restatement) ------------------------------------------------------
  * When the certificate fails at a critical point X of rank r (lambda_min(S(X)) < 0 with eigenvector v, a

@@ -145,6 +145,12 @@ int dpgo_graph_certify_ex(dpgo_graph g, int r, const double* X, int max_iters, i
 int dpgo_graph_certify_chol(dpgo_graph g, int r, const double* X, const double* w, double eta,
                             const dpgo_chol_cert_params* p, double* lambda_min, double* eigvec, double* f_relax,
                             dpgo_chol_cert_info* info);
+/* The block certificate (dpgo_hip_certify_block) on the whole graph's central edge-stream handle with the weights w
+ * (per edge in the graph's order; NULL: ones), the shape of dpgo_graph_certify_chol: any graph size, and with a
+ * robust run's final weights the certificate of the problem that run solved.  f_relax (optional) = f(X) with the
+ * same weights, evaluated first, so an error leaves every output untouched. */
+int dpgo_graph_certify_block(dpgo_graph g, int r, const double* X, const double* w, const dpgo_block_cert_params* p,
+                             double* lambda_min, double* eigvec, double* f_relax, dpgo_cert_info* info);
 /* The rank staircase's step for the whole graph, next to dpgo_graph_certify_ex: when that returned lambda_min < 0
  * at a critical point X of rank r, X_out ((r+1) x (d+1) n, column-major) = dpgo_hip_escape on the central
  * unit-weight edge-stream handle at rank r + 1, along dpgo_hip_escape_direction of eigvec_or_v (vec_rows x (d+1) n,
