@@ -364,6 +364,32 @@ int dpgo_graph_grid3d(int k, unsigned long long seed, double rot_sigma, double t
   return DPGO_HIP_OK;
 }
 
+// The poses dpgo_graph_grid3d measured: its first 4 n normals and its lattice coordinates, in the same order.
+int dpgo_graph_grid3d_truth(int k, unsigned long long seed, double* T_out) {
+  if (!T_out || k < 2 || k > 200) return fail(DPGO_HIP_EINVAL, "grid side must be in [2, 200] and T_out non-null");
+  const int n = k * k * k, kk = k * k;
+  SplitMix64 rng(seed);
+  for (int i = 0; i < n; ++i) {
+    double q[4];
+    for (double& x : q) x = rng.normal();
+    M3 Ri;
+    quat_rot(q, Ri);
+    const int z = i / kk;
+    int idx = i % kk;
+    if (z & 1) idx = kk - 1 - idx;
+    const int yy = idx / k;
+    int xx = idx % k;
+    if (yy & 1) xx = k - 1 - xx;
+    double* P = T_out + 12 * static_cast<size_t>(i);
+    for (int c = 0; c < 3; ++c)
+      for (int a = 0; a < 3; ++a) P[3 * c + a] = Ri[a][c];
+    P[9] = xx;
+    P[10] = yy;
+    P[11] = z;
+  }
+  return DPGO_HIP_OK;
+}
+
 int dpgo_graph_info(dpgo_graph g, int* d, int* n, int* m, int* duplicates) {
   if (!g) return fail(DPGO_HIP_EINVAL, "null graph");
   if (d) *d = g->d;

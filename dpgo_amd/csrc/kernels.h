@@ -495,6 +495,27 @@ constexpr int kEdgeErrThreads = 256;
 inline long edge_errors_blocks(long m) { return (m + kEdgeErrThreads - 1) / kEdgeErrThreads; }
 hipError_t launch_edge_errors(int r, int b, const EdgeList& E, const double* X, const double* X2, double* err,
                               double* rot_sq, double* tra_sq, double* cost, double* work, hipStream_t stream);
+// Trajectory evaluation against a ground truth (build-defined).  That (the estimate) and
+// T (the truth) are n SE(d) poses, d x (d+1) column-major each (launch_round_se's output); use: one int per pose,
+// null = every pose.  The pose kernels take kTrajSpans consecutive 64-pose spans per block and leave one partial per
+// block in `work` (traj_blocks(n) times the number of results), which one finishing launch joins in a fixed order.
+// No atomics: every result is a function of its inputs alone, whatever the pointer alignment.
+constexpr int kTrajSpans = 2;
+constexpr int kTrajSums = 5;
+inline long traj_blocks(long n) { return (n + 64L * kTrajSpans - 1) / (64L * kTrajSpans); }
+inline int traj_moments_len(int d) { return 3 + 2 * d + d * d; }
+// mom (device) = [count, sum |a|^2, sum |b|^2, sum a, sum b, sum b a^T], a = that_j - shift[0..d), b = t_j -
+// shift[d..2d) (shift: host, null = zeros); work: traj_blocks(n) traj_moments_len(d) doubles
+hipError_t launch_traj_moments(int d, long n, const double* That, const double* T, const int* use,
+                               const double* shift, double* mom, double* work, hipStream_t stream);
+// tra_sq[j] = |A that_j + a - t_j|^2, rot_sq[j] = |A Rhat_j - R_j|_F^2 (NaN for an unused pose), sums (device) =
+// [count, sum tra, sum rot, max tra, max rot]; Aa = [A | a] d x (d+1) column-major on the host, null = identity.
+// Any output may be null, not all; sums needs work: traj_blocks(n) kTrajSums doubles.
+hipError_t launch_traj_errors(int d, long n, const double* That, const double* T, const int* use, const double* Aa,
+                              double* tra_sq, double* rot_sq, double* sums, double* work, hipStream_t stream);
+// R_out[e] (d d row-major) = R_p1^T R_p2, t_out[e] = R_p1^T (t_p2 - t_p1) over m edges of T; indices trusted
+hipError_t launch_relative_poses(int d, long m, const int* p1, const int* p2, const double* T, double* R_out,
+                                 double* t_out, hipStream_t stream);
 // PGOAgent::computeConvergedLoopClosureRatio (src/PGOAgent.cpp:1247-1289): per agent a, the share of
 // its loop closures idx[off[a] .. off[a+1]) whose weight w[] is exactly 1 or 0 (0/0 = NaN, as there)
 hipError_t launch_conv_ratio(int num_agents, const int* off, const int* idx, const double* w, double* ratio,

@@ -3196,6 +3196,267 @@ __global__ __launch_bounds__(kEdgeFinishThreads) void k_edge_cost_finish(long bl
   }
 }
 
+// ---- trajectory evaluation against a ground truth (build-defined) ----
+// A 64-pose span of SE(D) poses (PW = D (D + 1) doubles each, PW even) into LDS at row stride PW + 1, as k_round_se
+// stages it: 16-byte chunks on a full, 16-byte-aligned span, 8-byte loads otherwise.  The staging moves bits only.
+template <int PW>
+__device__ __forceinline__ void traj_stage_span(double* sm, const double* __restrict__ src, int count, int t) {
+  constexpr int PS = PW + 1;
+  static_assert(PW % 2 == 0, "a 16-byte chunk never straddles two poses");
+  if (count == 64 && (reinterpret_cast<unsigned long>(src) & 15) == 0) {
+    constexpr int NV = PW / 2;
+    const double2* S2 = reinterpret_cast<const double2*>(src);
+    double2 v[NV];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) v[i] = S2[t + 64 * i];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int x = 2 * (t + 64 * i);
+      double* q = sm + (x / PW) * PS + x % PW;
+      q[0] = v[i].x;
+      q[1] = v[i].y;
+    }
+  } else {
+    const int total = count * PW;
+    for (int x = t; x < total; x += 64) sm[(x / PW) * PS + x % PW] = src[x];
+  }
+}
+
+// Moments of two trajectories' translations about a shift (sh = the estimate's, st = the truth's): with
+// a = fl(that_j - sh), b = fl(t_j - st) per used pose (use null = every pose, else use[j] != 0),
+//   [count, sum |a|^2, sum |b|^2, sum a (D), sum b (D), M = sum b a^T (D x D column-major)]   (3 + 2 D + D^2 sums).
+// k_gram's shape: block k takes the kTrajSpans consecutive 64-pose spans from pose 64 kTrajSpans k on, both
+// trajectories stream through LDS, thread t adds its pose's terms (a squared norm is one product and D - 1 FMAs, a
+// product b_i a_j one multiplication) to its sums, and one xor butterfly over the 64 lanes leaves the block's partial
+// (entry-major, for k_traj_finish).  The grid is a function of n alone.  No atomics.
+struct TrajShift {
+  double sh[3], st[3];
+};
+template <int D>
+__global__ __launch_bounds__(64) void k_traj_moments(long n, const double* __restrict__ That,
+                                                     const double* __restrict__ T, const int* __restrict__ use,
+                                                     TrajShift S, double* __restrict__ partial) {
+#pragma clang fp contract(off)
+  constexpr int PW = D * (D + 1), PS = PW + 1;
+  constexpr int P = 3 + 2 * D + D * D;
+  __shared__ double sa[64 * PS], sb[64 * PS];
+  const int t = static_cast<int>(threadIdx.x);
+  double acc[P];
+#pragma unroll
+  for (int i = 0; i < P; ++i) acc[i] = 0.0;
+#pragma unroll 1
+  for (int s = 0; s < kTrajSpans; ++s) {
+    const long first = (static_cast<long>(blockIdx.x) * kTrajSpans + s) * 64;
+    if (first >= n) break;  // block-uniform
+    const int count = n - first < 64 ? static_cast<int>(n - first) : 64;
+    if (s > 0) __syncthreads();  // the previous span has been read
+    traj_stage_span<PW>(sa, That + first * PW, count, t);
+    traj_stage_span<PW>(sb, T + first * PW, count, t);
+    __syncthreads();
+    if (t < count && (use == nullptr || use[first + t] != 0)) {
+      const double* pa = sa + t * PS + D * D;
+      const double* pb = sb + t * PS + D * D;
+      double a[D], b[D];
+#pragma unroll
+      for (int i = 0; i < D; ++i) {
+        a[i] = pa[i] - S.sh[i];
+        b[i] = pb[i] - S.st[i];
+      }
+      double na = a[0] * a[0], nb = b[0] * b[0];
+#pragma unroll
+      for (int i = 1; i < D; ++i) {
+        na = fma(a[i], a[i], na);
+        nb = fma(b[i], b[i], nb);
+      }
+      acc[0] += 1.0;
+      acc[1] += na;
+      acc[2] += nb;
+#pragma unroll
+      for (int i = 0; i < D; ++i) {
+        acc[3 + i] += a[i];
+        acc[3 + D + i] += b[i];
+      }
+#pragma unroll
+      for (int c = 0; c < D; ++c)
+#pragma unroll
+        for (int i = 0; i < D; ++i) acc[3 + 2 * D + c * D + i] += b[i] * a[c];
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < P; ++i) {
+    double v = acc[i];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    acc[i] = v;
+  }
+  if (t == 0) {
+    double* dst = partial + blockIdx.x;
+#pragma unroll
+    for (int i = 0; i < P; ++i) dst[static_cast<long>(i) * gridDim.x] = acc[i];
+  }
+}
+
+// Entry i (= the block) of the `blocks` entry-major partials into out[i], in k_gram_finish's order: thread t takes
+// partials t, t + 1024, ..., the xor butterfly joins each wave, thread 0 joins the 16 wave results in wave order.
+// Entries below nsum are sums, the others maxima (exact in any order).  A function of `blocks` alone.
+constexpr int kTrajFinishThreads = 1024;
+__global__ __launch_bounds__(kTrajFinishThreads) void k_traj_finish(long blocks, int nsum,
+                                                                    const double* __restrict__ partial,
+                                                                    double* __restrict__ out) {
+  __shared__ double ws[kTrajFinishThreads / 64];
+  const int i = static_cast<int>(blockIdx.x);
+  const int t = static_cast<int>(threadIdx.x);
+  const bool sum = i < nsum;  // block-uniform
+  const double* src = partial + static_cast<long>(i) * blocks;
+  double v = 0.0;  // the maxima are of squares: 0 is their identity too
+  if (sum) {
+    for (long g = t; g < blocks; g += kTrajFinishThreads) v += src[g];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+  } else {
+    for (long g = t; g < blocks; g += kTrajFinishThreads) v = fmax(v, src[g]);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
+  }
+  if ((t & 63) == 0) ws[t >> 6] = v;
+  __syncthreads();
+  if (t == 0) {
+    double s = ws[0];
+#pragma unroll
+    for (int k = 1; k < kTrajFinishThreads / 64; ++k) s = sum ? s + ws[k] : fmax(s, ws[k]);
+    out[i] = s;
+  }
+}
+
+// Per-pose errors of the estimate That against the truth T under the rigid map [A | a] (D x (D + 1) column-major in
+// the kernel arguments):
+//   tra_sq[j] = |A that_j + a - t_j|^2,   rot_sq[j] = |A Rhat_j - R_j|_F^2   (chordal).
+// One operation order per D, the same for every pose, block and pointer alignment:
+//   per row i: v = A[i,0] that[0], then D - 1 FMAs, v = v + a[i], rho = v - t[i], tra = fma(rho, rho, tra);
+//   per column c, per row i: v = A[i,0] Rhat[0,c], then D - 1 FMAs, df = v - R[i,c], rot = fma(df, df, rot).
+// An unused pose (use[j] == 0) gets a quiet NaN in both outputs and takes no part in the block's partial
+// [count, sum tra, sum rot, max tra, max rot] (entry-major; k_traj_moments' shape, spans, butterfly and finish).
+struct TrajAa {
+  double v[12];
+};
+template <int D>
+__global__ __launch_bounds__(64) void k_traj_errors(long n, const double* __restrict__ That,
+                                                    const double* __restrict__ T, const int* __restrict__ use,
+                                                    TrajAa Aa, double* __restrict__ tra_sq,
+                                                    double* __restrict__ rot_sq, double* __restrict__ partial) {
+#pragma clang fp contract(off)
+  constexpr int PW = D * (D + 1), PS = PW + 1;
+  __shared__ double sa[64 * PS], sb[64 * PS];
+  const int t = static_cast<int>(threadIdx.x);
+  double acc[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll 1
+  for (int s = 0; s < kTrajSpans; ++s) {
+    const long first = (static_cast<long>(blockIdx.x) * kTrajSpans + s) * 64;
+    if (first >= n) break;  // block-uniform
+    const int count = n - first < 64 ? static_cast<int>(n - first) : 64;
+    if (s > 0) __syncthreads();
+    traj_stage_span<PW>(sa, That + first * PW, count, t);
+    traj_stage_span<PW>(sb, T + first * PW, count, t);
+    __syncthreads();
+    if (t < count) {
+      const long j = first + t;
+      if (use == nullptr || use[j] != 0) {
+        const double* pa = sa + t * PS;
+        const double* pb = sb + t * PS;
+        double tra = 0.0, rot = 0.0;
+#pragma unroll
+        for (int i = 0; i < D; ++i) {
+          double v = Aa.v[i] * pa[D * D];
+#pragma unroll
+          for (int k = 1; k < D; ++k) v = fma(Aa.v[k * D + i], pa[D * D + k], v);
+          v = v + Aa.v[D * D + i];
+          const double rho = v - pb[D * D + i];
+          tra = fma(rho, rho, tra);
+        }
+#pragma unroll
+        for (int c = 0; c < D; ++c)
+#pragma unroll
+          for (int i = 0; i < D; ++i) {
+            double v = Aa.v[i] * pa[c * D];
+#pragma unroll
+            for (int k = 1; k < D; ++k) v = fma(Aa.v[k * D + i], pa[c * D + k], v);
+            const double df = v - pb[c * D + i];
+            rot = fma(df, df, rot);
+          }
+        if (tra_sq) tra_sq[j] = tra;
+        if (rot_sq) rot_sq[j] = rot;
+        acc[0] += 1.0;
+        acc[1] += tra;
+        acc[2] += rot;
+        acc[3] = fmax(acc[3], tra);
+        acc[4] = fmax(acc[4], rot);
+      } else {
+        const double qnan = __longlong_as_double(0x7ff8000000000000LL);
+        if (tra_sq) tra_sq[j] = qnan;
+        if (rot_sq) rot_sq[j] = qnan;
+      }
+    }
+  }
+  if (partial == nullptr) return;  // uniform over the grid
+#pragma unroll
+  for (int i = 0; i < 5; ++i) {
+    double v = acc[i];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+      const double o = __shfl_xor(v, off, 64);
+      v = i < 3 ? v + o : fmax(v, o);
+    }
+    acc[i] = v;
+  }
+  if (t == 0) {
+    double* dst = partial + blockIdx.x;
+#pragma unroll
+    for (int i = 0; i < 5; ++i) dst[static_cast<long>(i) * gridDim.x] = acc[i];
+  }
+}
+
+// Relative poses of a trajectory T over an edge list, one thread per edge (two gathered poses in, D^2 + D doubles
+// out, as dpgo_edges takes them):
+//   R_out[e] (row-major) = R_p1^T R_p2,   t_out[e] = R_p1^T (t_p2 - t_p1).
+// Entry (u, c): R1[0,u] R2[0,c], then D - 1 FMAs; t_out[u]: dt = t2 - t1 per component, R1[0,u] dt[0], then D - 1
+// FMAs.  The same order for every edge: an edge's outputs depend on its two poses alone.
+template <int D>
+__global__ __launch_bounds__(kEdgeErrThreads) void k_relative_poses(long m, const int* __restrict__ p1,
+                                                                    const int* __restrict__ p2,
+                                                                    const double* __restrict__ T,
+                                                                    double* __restrict__ R_out,
+                                                                    double* __restrict__ t_out) {
+#pragma clang fp contract(off)
+  constexpr int PW = D * (D + 1);
+  const long e = static_cast<long>(blockIdx.x) * kEdgeErrThreads + threadIdx.x;
+  if (e >= m) return;
+  const double* P1 = T + static_cast<long>(p1[e]) * PW;
+  const double* P2 = T + static_cast<long>(p2[e]) * PW;
+  double a[PW], b[PW];
+#pragma unroll
+  for (int x = 0; x < PW; ++x) {
+    a[x] = P1[x];
+    b[x] = P2[x];
+  }
+  double dt[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) dt[k] = b[D * D + k] - a[D * D + k];
+#pragma unroll
+  for (int u = 0; u < D; ++u) {
+#pragma unroll
+    for (int c = 0; c < D; ++c) {
+      double v = a[u * D] * b[c * D];
+#pragma unroll
+      for (int k = 1; k < D; ++k) v = fma(a[u * D + k], b[c * D + k], v);
+      R_out[e * (D * D) + u * D + c] = v;
+    }
+    double w = a[u * D] * dt[0];
+#pragma unroll
+    for (int k = 1; k < D; ++k) w = fma(a[u * D + k], dt[k], w);
+    t_out[e * D + u] = w;
+  }
+}
+
 // Nesterov updateV deferred into the colour's next combination pass (one pass instead of two):
 //   V' = project(V + gv (X - Yv))   (updateV, src/PGOAgent.cpp:1086-1091, of the agent's last update)
 //   out = project(sa X + sb V')     (updateY / the iterate(false) step, :1077-1084, of the next iteration)
@@ -5612,6 +5873,64 @@ hipError_t launch_edge_errors(int r, int b, const EdgeList& E, const double* X, 
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess || !cost) return e;
   k_edge_cost_finish<<<1, kEdgeFinishThreads, 0, stream>>>(blocks, work, cost);
+  return hipGetLastError();
+}
+
+hipError_t launch_traj_moments(int d, long n, const double* That, const double* T, const int* use,
+                               const double* shift, double* mom, double* work, hipStream_t stream) {
+  if ((d != 2 && d != 3) || n <= 0 || !That || !T || !mom || !work) return hipErrorInvalidValue;
+  const long blocks = traj_blocks(n);
+  if (blocks > 0x7fffffffL) return hipErrorInvalidValue;
+  const dim3 grid(static_cast<unsigned>(blocks));
+  TrajShift S{};
+  if (shift != nullptr)
+    for (int i = 0; i < d; ++i) {
+      S.sh[i] = shift[i];
+      S.st[i] = shift[d + i];
+    }
+  if (d == 2)
+    k_traj_moments<2><<<grid, 64, 0, stream>>>(n, That, T, use, S, work);
+  else
+    k_traj_moments<3><<<grid, 64, 0, stream>>>(n, That, T, use, S, work);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const int P = traj_moments_len(d);
+  k_traj_finish<<<P, kTrajFinishThreads, 0, stream>>>(blocks, P, work, mom);
+  return hipGetLastError();
+}
+
+hipError_t launch_traj_errors(int d, long n, const double* That, const double* T, const int* use, const double* Aa,
+                              double* tra_sq, double* rot_sq, double* sums, double* work, hipStream_t stream) {
+  if ((d != 2 && d != 3) || n <= 0 || !That || !T) return hipErrorInvalidValue;
+  if (!tra_sq && !rot_sq && !sums) return hipErrorInvalidValue;
+  if (sums != nullptr && work == nullptr) return hipErrorInvalidValue;
+  const long blocks = traj_blocks(n);
+  if (blocks > 0x7fffffffL) return hipErrorInvalidValue;
+  const dim3 grid(static_cast<unsigned>(blocks));
+  TrajAa A{};
+  for (int c = 0; c <= d; ++c)
+    for (int i = 0; i < d; ++i) A.v[c * d + i] = Aa != nullptr ? Aa[c * d + i] : (i == c ? 1.0 : 0.0);
+  double* partial = sums ? work : nullptr;
+  if (d == 2)
+    k_traj_errors<2><<<grid, 64, 0, stream>>>(n, That, T, use, A, tra_sq, rot_sq, partial);
+  else
+    k_traj_errors<3><<<grid, 64, 0, stream>>>(n, That, T, use, A, tra_sq, rot_sq, partial);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess || !sums) return e;
+  k_traj_finish<<<kTrajSums, kTrajFinishThreads, 0, stream>>>(blocks, 3, work, sums);
+  return hipGetLastError();
+}
+
+hipError_t launch_relative_poses(int d, long m, const int* p1, const int* p2, const double* T, double* R_out,
+                                 double* t_out, hipStream_t stream) {
+  if ((d != 2 && d != 3) || m <= 0 || !p1 || !p2 || !T || !R_out || !t_out) return hipErrorInvalidValue;
+  const long blocks = edge_errors_blocks(m);
+  if (blocks > 0x7fffffffL) return hipErrorInvalidValue;
+  const dim3 grid(static_cast<unsigned>(blocks));
+  if (d == 2)
+    k_relative_poses<2><<<grid, kEdgeErrThreads, 0, stream>>>(m, p1, p2, T, R_out, t_out);
+  else
+    k_relative_poses<3><<<grid, kEdgeErrThreads, 0, stream>>>(m, p1, p2, T, R_out, t_out);
   return hipGetLastError();
 }
 

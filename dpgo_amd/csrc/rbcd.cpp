@@ -127,6 +127,11 @@ struct dpgo_rbcd_s {
   DevBuf<double> Tround;           // the owned poses rounded to SE(d), d x b per pose
   // rank reduction (dpgo_rbcd_gram / _get_X_reduced): C then k_gram's partials; the owned poses at rank k
   DevBuf<double> gram_cw, Xreduced;
+  // evaluation against a ground truth (dpgo_rbcd_set_truth / _truth_moments / _truth_errors): the owned poses'
+  // truth (d x b per pose, the engine's pose order) and mask; the moments or [tra_sq, rot_sq, sums], then the partials
+  DevBuf<double> truth_T, truth_out;
+  DevBuf<int> truth_use;
+  bool truth_set = false, truth_masked = false;
   // trajectory read-in (dpgo_rbcd_set_trajectory): the owned poses' d x b blocks, then the K frames, staged for
   // k_frame_lift; the owned poses' global agent ids, built at the first call with frames
   DevBuf<double> Tin;
@@ -979,6 +984,107 @@ int dpgo_rbcd_get_trajectory(dpgo_rbcd e, const double* anchor, double* Tg) {
   HIP_TRY(hipStreamSynchronize(e->stream));
   for (long q = 0; q < e->Nown; ++q)
     std::memcpy(Tg + static_cast<size_t>(e->own_global[q]) * dbs, &host[q * dbs], sizeof(double) * dbs);
+  return DPGO_HIP_OK;
+}
+
+int dpgo_rbcd_set_truth(dpgo_rbcd e, const double* Tg, const int* use_global) {
+  if (!e) return fail(DPGO_HIP_EINVAL, "null engine");
+  if (!Tg) {
+    e->truth_set = e->truth_masked = false;
+    return DPGO_HIP_OK;
+  }
+  e->truth_set = true;
+  e->truth_masked = use_global != nullptr;
+  if (e->Nown == 0) return DPGO_HIP_OK;
+  const size_t dbs = static_cast<size_t>(e->d) * e->b;
+  std::vector<double> host(static_cast<size_t>(e->Nown) * dbs);
+  std::vector<int> mask(use_global ? e->Nown : 0);
+  for (long q = 0; q < e->Nown; ++q) {
+    std::memcpy(&host[q * dbs], Tg + static_cast<size_t>(e->own_global[q]) * dbs, sizeof(double) * dbs);
+    if (use_global) mask[q] = use_global[e->own_global[q]];
+  }
+  e->truth_set = false;  // until both are on the device
+  DPGO_TRY(upload_vec(e->truth_T, host, e->stream));
+  if (use_global) DPGO_TRY(upload_vec(e->truth_use, mask, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));  // the staging vectors leave with this call
+  e->truth_set = true;
+  return DPGO_HIP_OK;
+}
+
+namespace {
+// dpgo_rbcd_get_trajectory's rounding of the owned poses into e->Tround, in the frame of `anchor` (r b host doubles,
+// staged behind the rounded poses) or of the engine's own global pose 0
+int round_owned(dpgo_rbcd e, const double* anchor) {
+  const size_t rbs = e->rb(), dbs = static_cast<size_t>(e->d) * e->b;
+  HIP_TRY(e->Tround.ensure(static_cast<size_t>(e->Nown) * dbs + rbs));
+  const double* anchor_dev = e->X.p + static_cast<size_t>(anchor ? 0 : e->own_of_global[0]) * rbs;
+  if (anchor) {
+    double* stage = e->Tround.p + static_cast<size_t>(e->Nown) * dbs;
+    HIP_TRY(hipMemcpyAsync(stage, anchor, sizeof(double) * rbs, hipMemcpyHostToDevice, e->stream));
+    anchor_dev = stage;
+  }
+  return dpgo_hip_round_se_dev(e->r, e->d, e->Nown, e->X.p, anchor_dev, e->Tround.p, e->stream);
+}
+
+int check_truth_call(dpgo_rbcd e, const double* anchor) {
+  if (!e) return fail(DPGO_HIP_EINVAL, "null engine");
+  if (!e->truth_set) return fail(DPGO_HIP_EINVAL, "no ground truth set (dpgo_rbcd_set_truth)");
+  if (!anchor && e->own_of_global[0] < 0)
+    return fail(DPGO_HIP_EINVAL, "no anchor given and global pose 0 belongs to another rank (dpgo_rbcd_get_anchor)");
+  return DPGO_HIP_OK;
+}
+}  // namespace
+
+int dpgo_rbcd_truth_moments(dpgo_rbcd e, const double* anchor, const double* shift, double* mom) {
+  DPGO_TRY(check_truth_call(e, anchor));
+  if (!mom) return fail(DPGO_HIP_EINVAL, "truth_moments: null mom");
+  const size_t P = DPGO_TRAJ_MOMENTS(e->d);
+  if (e->Nown == 0) {  // a rank without poses contributes nothing to the sums
+    std::fill(mom, mom + P, 0.0);
+    return DPGO_HIP_OK;
+  }
+  DPGO_TRY(join_side(e));
+  DPGO_TRY(round_owned(e, anchor));
+  HIP_TRY(e->truth_out.ensure(P + static_cast<size_t>(dpgo_hip_traj_moments_work_doubles(e->d, e->Nown))));
+  DPGO_TRY(dpgo_hip_traj_moments_dev(e->d, e->Nown, e->Tround.p, e->truth_T.p,
+                                     e->truth_masked ? e->truth_use.p : nullptr, shift, e->truth_out.p,
+                                     e->truth_out.p + P, e->stream));
+  HIP_TRY(hipMemcpyAsync(mom, e->truth_out.p, sizeof(double) * P, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return DPGO_HIP_OK;
+}
+
+int dpgo_rbcd_truth_errors(dpgo_rbcd e, const double* anchor, const double* Aa, double* tra_sq_global,
+                           double* rot_sq_global, double* sums) {
+  DPGO_TRY(check_truth_call(e, anchor));
+  if (!tra_sq_global && !rot_sq_global && !sums) return fail(DPGO_HIP_EINVAL, "truth_errors: no output requested");
+  if (e->Nown == 0) {
+    if (sums) std::fill(sums, sums + DPGO_TRAJ_SUMS, 0.0);
+    return DPGO_HIP_OK;
+  }
+  DPGO_TRY(join_side(e));
+  DPGO_TRY(round_owned(e, anchor));
+  const size_t N = static_cast<size_t>(e->Nown);
+  HIP_TRY(e->truth_out.ensure(2 * N + DPGO_TRAJ_SUMS +
+                              static_cast<size_t>(dpgo_hip_traj_errors_work_doubles(e->d, e->Nown))));
+  double* o = e->truth_out.p;  // tra_sq, rot_sq, sums, partials
+  DPGO_TRY(dpgo_hip_traj_errors_dev(e->d, e->Nown, e->Tround.p, e->truth_T.p,
+                                    e->truth_masked ? e->truth_use.p : nullptr, Aa, tra_sq_global ? o : nullptr,
+                                    rot_sq_global ? o + N : nullptr, sums ? o + 2 * N : nullptr,
+                                    o + 2 * N + DPGO_TRAJ_SUMS, e->stream));
+  std::vector<double> host(2 * N);
+  if (tra_sq_global)
+    HIP_TRY(hipMemcpyAsync(host.data(), o, sizeof(double) * N, hipMemcpyDeviceToHost, e->stream));
+  if (rot_sq_global)
+    HIP_TRY(hipMemcpyAsync(host.data() + N, o + N, sizeof(double) * N, hipMemcpyDeviceToHost, e->stream));
+  double s[DPGO_TRAJ_SUMS];
+  if (sums) HIP_TRY(hipMemcpyAsync(s, o + 2 * N, sizeof(s), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  for (long q = 0; q < e->Nown; ++q) {
+    if (tra_sq_global) tra_sq_global[e->own_global[q]] = host[q];
+    if (rot_sq_global) rot_sq_global[e->own_global[q]] = host[N + q];
+  }
+  if (sums) std::memcpy(sums, s, sizeof(s));
   return DPGO_HIP_OK;
 }
 

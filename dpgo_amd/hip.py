@@ -89,6 +89,18 @@ class Edges(C.Structure):
                 ("kappa", C.c_void_p), ("tau", C.c_void_p), ("w", C.c_void_p)]
 
 
+class AlignInfo(C.Structure):
+    """dpgo_align_info (include/dpgo_hip.h)."""
+    _fields_ = [("count", C.c_double), ("sigma", C.c_double * 3), ("rank", C.c_int)]
+
+
+class EvalInfo(C.Structure):
+    """dpgo_eval_info (include/dpgo_rbcd.h)."""
+    _fields_ = [("count", C.c_double), ("Aa", C.c_double * 12), ("sigma", C.c_double * 3), ("rank", C.c_int),
+                ("ate_rmse", C.c_double), ("ate_max", C.c_double), ("rot_rmse", C.c_double), ("rot_max", C.c_double),
+                ("rpe_tra_rmse", C.c_double), ("rpe_rot_rmse", C.c_double), ("edges_used", C.c_double)]
+
+
 class DPGOHipError(RuntimeError):
     code = 0  # the C ABI's return code where one raised it
 
@@ -146,6 +158,19 @@ _SIGS = [
     ("dpgo_hip_edge_errors_work_doubles", [C.c_longlong], C.c_longlong),
     ("dpgo_hip_edge_errors_dev", [C.c_int, C.c_int, C.c_longlong, C.POINTER(Edges), C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    ("dpgo_hip_traj_moments", [C.c_int, C.c_int, _dp, _dp, _ip, _dp, _dp], C.c_int),
+    ("dpgo_hip_traj_moments_work_doubles", [C.c_int, C.c_longlong], C.c_longlong),
+    ("dpgo_hip_traj_moments_dev", [C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, _dp, C.c_void_p,
+                                   C.c_void_p, C.c_void_p], C.c_int),
+    ("dpgo_hip_align_moments", [C.c_int, _dp, _dp, C.c_double, _dp, C.POINTER(AlignInfo)], C.c_int),
+    ("dpgo_hip_traj_align", [C.c_int, C.c_int, _dp, _dp, _ip, _dp, C.POINTER(AlignInfo)], C.c_int),
+    ("dpgo_hip_traj_errors", [C.c_int, C.c_int, _dp, _dp, _ip, _dp, _dp, _dp, _dp], C.c_int),
+    ("dpgo_hip_traj_errors_work_doubles", [C.c_int, C.c_longlong], C.c_longlong),
+    ("dpgo_hip_traj_errors_dev", [C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, _dp, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    ("dpgo_hip_relative_poses", [C.c_int, C.c_int, _dp, C.c_int, _ip, _ip, _dp, _dp], C.c_int),
+    ("dpgo_hip_relative_poses_dev", [C.c_int, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
     ("dpgo_hip_optimize", [C.c_void_p, C.POINTER(OptParams), _dp, _dp, C.POINTER(OptResult)], C.c_int),
     ("dpgo_hip_f_dev", [C.c_void_p, C.c_void_p, _dp], C.c_int),
     ("dpgo_hip_egrad_dev", [C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
@@ -884,6 +909,196 @@ def edge_errors_dev(r, d, n, m, p1_dev: int, p2_dev: int, R_dev: int, t_dev: int
                                           C.c_void_p(work_dev or 0), C.c_void_p(stream_ptr or 0)))
 
 
+# ---- trajectory evaluation against a ground truth (dpgo_hip_traj_*, include/dpgo_hip.h) ----
+TRAJ_SUMS = 5
+
+
+def traj_moments_len(d) -> int:
+    """DPGO_TRAJ_MOMENTS(d)."""
+    return 3 + 2 * d + d * d
+
+
+def _traj_flat(T, d, what="trajectory"):
+    """A d x (d+1) n matrix, or the flat column-major buffer of one, as (flat float64 buffer, n)."""
+    T = np.asarray(T, dtype=np.float64)
+    flat = np.ascontiguousarray(T.T).ravel() if T.ndim == 2 else np.ascontiguousarray(T).ravel()
+    if (T.ndim == 2 and T.shape[0] != d) or flat.size % (d * (d + 1)) != 0:
+        raise DPGOHipError(f"{what}: need d x (d+1) n with d = {d}")
+    return flat, flat.size // (d * (d + 1))
+
+
+def _traj_pair(That, T, d, use):
+    a, n = _traj_flat(That, d, "That")
+    b, nb = _traj_flat(T, d, "T")
+    if nb != n:
+        raise DPGOHipError("That and T must have the same number of poses")
+    u = None
+    if use is not None:
+        u, _ = _i32(use)
+        if u.size != n:
+            raise DPGOHipError("use must have one entry per pose")
+    return a, b, u, n
+
+
+def _opt_ptr(a, ptype=_dp):
+    return a.ctypes.data_as(ptype) if a is not None else None
+
+
+def _opt_vec(v, size, what):
+    if v is None:
+        return None
+    a = np.ascontiguousarray(np.asarray(v, dtype=np.float64).ravel())
+    if a.size != size:
+        raise DPGOHipError(f"{what} must have {size} entries")
+    return a
+
+
+def traj_moments(That, T, d, use=None, shift=None):
+    """mom = [count, sum |a|^2, sum |b|^2, sum a, sum b, M = sum b a^T (column-major)] of the translations of the
+    estimate That and the truth T (d x (d+1) n each) about shift = (s^, s) (2 d, None = zeros), over the poses with
+    use[j] != 0 (None = all), on the device: bitwise repeatable, additive over disjoint pose sets."""
+    a, b, u, n = _traj_pair(That, T, d, use)
+    s = _opt_vec(shift, 2 * d, "shift")
+    mom = np.empty(traj_moments_len(d))
+    _check(lib().dpgo_hip_traj_moments(int(d), n, a.ctypes.data_as(_dp), b.ctypes.data_as(_dp), _opt_ptr(u, _ip),
+                                       _opt_ptr(s), mom.ctypes.data_as(_dp)))
+    return mom
+
+
+def traj_moments_work_doubles(d, n) -> int:
+    return int(lib().dpgo_hip_traj_moments_work_doubles(int(d), int(n)))
+
+
+def traj_moments_dev(d, n, That_dev: int, T_dev: int, use_dev: int | None, shift, mom_dev: int, work_dev: int,
+                     stream_ptr: int | None = None):
+    """traj_moments on device pointers (shift: host, None = zeros; work_dev: traj_moments_work_doubles), queued on
+    `stream_ptr` (None = the null stream) without synchronisation."""
+    s = _opt_vec(shift, 2 * int(d), "shift")
+    _check(lib().dpgo_hip_traj_moments_dev(int(d), int(n), C.c_void_p(That_dev), C.c_void_p(T_dev),
+                                           C.c_void_p(use_dev or 0), _opt_ptr(s), C.c_void_p(mom_dev),
+                                           C.c_void_p(work_dev), C.c_void_p(stream_ptr or 0)))
+
+
+def _align_result(d, Aa, info):
+    return Aa.reshape(d + 1, d).T.copy(), dict(count=info.count, sigma=np.array(info.sigma[:d]), rank=info.rank)
+
+
+def align_moments(d, mom, shift=None, rank_tol=1e-12):
+    """(Aa, info) from traj_moments' vector (the sum of the ranks' vectors): Aa = [A | a] (d x (d+1)) minimises
+    sum |A t^_j + a - t_j|^2 over SE(d); info = dict(count, sigma (descending, the last signed by det(U V^T)),
+    rank = #{sigma_i > rank_tol sigma_1}).  Host only."""
+    m = _opt_vec(mom, traj_moments_len(d), "mom")
+    s = _opt_vec(shift, 2 * d, "shift")
+    Aa, info = np.empty(d * (d + 1)), AlignInfo()
+    _check(lib().dpgo_hip_align_moments(int(d), _opt_ptr(s), _opt_ptr(m), float(rank_tol), Aa.ctypes.data_as(_dp),
+                                        C.byref(info)))
+    return _align_result(d, Aa, info)
+
+
+def traj_align(That, T, d, use=None):
+    """(Aa, info) of align_moments from two moment launches on the device: the first gives the means, the second
+    takes the moments about them."""
+    a, b, u, n = _traj_pair(That, T, d, use)
+    Aa, info = np.empty(d * (d + 1)), AlignInfo()
+    _check(lib().dpgo_hip_traj_align(int(d), n, a.ctypes.data_as(_dp), b.ctypes.data_as(_dp), _opt_ptr(u, _ip),
+                                     Aa.ctypes.data_as(_dp), C.byref(info)))
+    return _align_result(d, Aa, info)
+
+
+def _aa_colmajor(Aa, d):
+    if Aa is None:
+        return None
+    A = np.asarray(Aa, dtype=np.float64)
+    if A.shape != (d, d + 1):
+        raise DPGOHipError(f"Aa must be d x (d+1) = {d} x {d + 1}")
+    return np.ascontiguousarray(A.T).ravel()
+
+
+def traj_errors(That, T, d, use=None, Aa=None, outputs=None):
+    """Per-pose errors of That against T under Aa = [A | a] (d x (d+1), None = identity), on the device:
+    dict(tra_sq [n] = |A t^_j + a - t_j|^2, rot_sq [n] = |A R^_j - R_j|_F^2, sums = [count, sum tra_sq, sum rot_sq,
+    max tra_sq, max rot_sq]); an unused pose has NaN and takes no part in sums.  outputs: the subset of those names
+    to compute (None = all three)."""
+    a, b, u, n = _traj_pair(That, T, d, use)
+    names = ("tra_sq", "rot_sq", "sums")
+    want = names if outputs is None else tuple(outputs)
+    bad = [k for k in want if k not in names]
+    if bad:
+        raise DPGOHipError(f"traj_errors: unknown output {bad[0]}")
+    out = {k: np.empty(TRAJ_SUMS if k == "sums" else n) for k in want}
+    A = _aa_colmajor(Aa, d)
+    _check(lib().dpgo_hip_traj_errors(int(d), n, a.ctypes.data_as(_dp), b.ctypes.data_as(_dp), _opt_ptr(u, _ip),
+                                      _opt_ptr(A), *[_opt_ptr(out.get(k)) for k in names]))
+    return out
+
+
+def traj_errors_work_doubles(d, n) -> int:
+    return int(lib().dpgo_hip_traj_errors_work_doubles(int(d), int(n)))
+
+
+def traj_errors_dev(d, n, That_dev: int, T_dev: int, use_dev: int | None, Aa, tra_sq_dev: int | None = None,
+                    rot_sq_dev: int | None = None, sums_dev: int | None = None, work_dev: int | None = None,
+                    stream_ptr: int | None = None):
+    """traj_errors on device pointers (Aa: host, None = identity; work_dev: traj_errors_work_doubles, needed with
+    sums_dev), queued on `stream_ptr` (None = the null stream) without synchronisation."""
+    A = _aa_colmajor(Aa, int(d))
+    _check(lib().dpgo_hip_traj_errors_dev(int(d), int(n), C.c_void_p(That_dev), C.c_void_p(T_dev),
+                                          C.c_void_p(use_dev or 0), _opt_ptr(A), C.c_void_p(tra_sq_dev or 0),
+                                          C.c_void_p(rot_sq_dev or 0), C.c_void_p(sums_dev or 0),
+                                          C.c_void_p(work_dev or 0), C.c_void_p(stream_ptr or 0)))
+
+
+def relative_poses(T, d, p1, p2):
+    """(R [m x d x d], t [m x d]) of the trajectory T (d x (d+1) n) over the edges (p1, p2), on the device:
+    R[e] = R_p1^T R_p2, t[e] = R_p1^T (t_p2 - t_p1), the form edge_errors takes measurements in."""
+    a, n = _traj_flat(T, d, "T")
+    a1, a1p = _i32(p1)
+    a2, a2p = _i32(p2)
+    m = a1.size
+    if a2.size != m:
+        raise DPGOHipError("relative_poses: p1 and p2 must have the same length")
+    R, t = np.empty(max(m, 1) * d * d), np.empty(max(m, 1) * d)
+    _check(lib().dpgo_hip_relative_poses(int(d), n, a.ctypes.data_as(_dp), m, a1p, a2p, R.ctypes.data_as(_dp),
+                                         t.ctypes.data_as(_dp)))
+    return R[:m * d * d].reshape(m, d, d), t[:m * d].reshape(m, d)
+
+
+def relative_poses_dev(d, n, T_dev: int, m, p1_dev: int, p2_dev: int, R_out_dev: int, t_out_dev: int,
+                       stream_ptr: int | None = None):
+    """relative_poses on device pointers (int32 indices, trusted), queued on `stream_ptr` without synchronisation."""
+    _check(lib().dpgo_hip_relative_poses_dev(int(d), int(n), C.c_void_p(T_dev), int(m), C.c_void_p(p1_dev),
+                                             C.c_void_p(p2_dev), C.c_void_p(R_out_dev), C.c_void_p(t_out_dev),
+                                             C.c_void_p(stream_ptr or 0)))
+
+
+def rot_angle(rot_sq):
+    """The angle (rad) of a chordal rotation error |A R^ - R|_F^2 for d = 2 and 3: 2 asin(min(1, sqrt(rot_sq / 8)))."""
+    return 2.0 * np.arcsin(np.minimum(1.0, np.sqrt(np.asarray(rot_sq, dtype=np.float64) / 8.0)))
+
+
+def merge_traj_sums(parts):
+    """traj_errors' sums of disjoint pose sets (one per rank) as one: entries 0-2 add, 3-4 take the maximum."""
+    P = np.asarray(parts, dtype=np.float64).reshape(-1, TRAJ_SUMS)
+    return np.concatenate([P[:, :3].sum(axis=0), P[:, 3:].max(axis=0)])
+
+
+def g2o_read_vertices(path, d, n):
+    """(T [d x (d+1) n], present [n]) from the VERTEX_SE2 / VERTEX_SE3:QUAT lines of a g2o file: the quaternion is
+    normalised (a reference pose must be a rotation); an absent id has present = 0 and NaN poses.  Host only."""
+    T = np.empty(d * (d + 1) * int(n))
+    present = np.empty(int(n), np.int32)
+    _check(lib().dpgo_g2o_read_vertices(str(path).encode(), int(d), int(n), T.ctypes.data_as(_dp),
+                                        present.ctypes.data_as(_ip)))
+    return from_dev_layout(T, d), present
+
+
+def grid3d_truth(k, seed=0):
+    """The 3 x 4 k^3 ground-truth trajectory Graph.grid3d(k, seed, ..) measured.  Host only."""
+    T = np.empty(12 * int(k) ** 3 if 2 <= int(k) <= 200 else 1)
+    _check(lib().dpgo_graph_grid3d_truth(int(k), int(seed), T.ctypes.data_as(_dp)))
+    return from_dev_layout(T, 3)
+
+
 # ----------------------------------------------------------------------------------------
 # Pose graphs + multi-agent RBCD engine (include/dpgo_rbcd.h)
 # ----------------------------------------------------------------------------------------
@@ -918,6 +1133,7 @@ class InitParams(C.Structure):
 
 LOCAL_INIT = {"chordal": 0, "odometry": 1}
 ALIGN = {"l2": 0, "robust": 1}
+EVAL_ALIGN = {"none": 0, "pose": 1, "lsq": 2}  # DPGO_ALIGN_NONE / _POSE / _LSQ of dpgo_graph_evaluate
 _ubp = C.POINTER(C.c_ubyte)
 
 _lp = C.POINTER(C.c_longlong)
@@ -946,6 +1162,13 @@ _SIGS2 = [
                            C.POINTER(EscapeInfo)], C.c_int),
     ("dpgo_graph_rank_reduce", [C.c_void_p, C.c_int, _dp, C.c_double, _ip, _dp, C.POINTER(RankInfo)], C.c_int),
     ("dpgo_graph_edge_errors", [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp], C.c_int),
+    ("dpgo_graph_grid3d_truth", [C.c_int, C.c_ulonglong, _dp], C.c_int),
+    ("dpgo_g2o_read_vertices", [C.c_char_p, C.c_int, C.c_int, _dp, _ip], C.c_int),
+    ("dpgo_graph_evaluate", [C.c_void_p, C.c_int, _dp, _dp, _ip, C.c_int, C.c_int, C.POINTER(EvalInfo), _dp, _dp, _dp,
+                             _dp], C.c_int),
+    ("dpgo_rbcd_set_truth", [C.c_void_p, _dp, _ip], C.c_int),
+    ("dpgo_rbcd_truth_moments", [C.c_void_p, _dp, _dp, _dp], C.c_int),
+    ("dpgo_rbcd_truth_errors", [C.c_void_p, _dp, _dp, _dp, _dp, _dp], C.c_int),
     ("dpgo_rbcd_get_errors", [C.c_void_p, C.c_void_p, C.c_int, _dp, _dp, _dp, _dp], C.c_int),
     ("dpgo_rbcd_gram", [C.c_void_p, _dp], C.c_int),
     ("dpgo_rbcd_get_X_reduced", [C.c_void_p, C.c_int, _dp, _dp], C.c_int),
@@ -1037,7 +1260,15 @@ class Graph:
     def grid3d(cls, k, seed=0, rot_sigma=0.2, trans_sigma=0.1):
         h = C.c_void_p()
         _check(lib().dpgo_graph_grid3d(int(k), int(seed), rot_sigma, trans_sigma, C.byref(h)))
-        return cls(h)
+        g = cls(h)
+        g._grid = (int(k), int(seed))
+        return g
+
+    def truth(self):
+        """The ground-truth trajectory (3 x 4 n) a grid graph measured (grid3d_truth of its side and seed)."""
+        if getattr(self, "_grid", None) is None:
+            raise DPGOHipError("truth: not a grid graph")
+        return grid3d_truth(*self._grid)
 
     @classmethod
     def from_arrays(cls, d, n, p1, p2, R, t, kappa, tau):
@@ -1286,6 +1517,43 @@ class Graph:
         _check(lib().dpgo_graph_edge_errors(self.h, int(r), flat.ctypes.data_as(_dp), wp, *ptrs))
         return _edge_result(out, self.m)
 
+    def evaluate(self, X, r, T_truth, use=None, align="lsq", pose=0, per_item=True):
+        """A solution X (flat r x (d+1) n column-major buffer or the matrix) against the truth T_truth (d x (d+1) n),
+        on the device: rounded in the frame of its pose `pose` when r > d, aligned ("none", "pose", "lsq"), then
+        ATE and RPE over the graph's own edges.  dict(count, Aa [d x (d+1)], sigma, rank, ate_rmse, ate_max, rot_rmse,
+        rot_max, rpe_tra_rmse, rpe_rot_rmse, edges_used) and, with per_item, tra_sq [n], rot_sq [n], rpe_rot_sq [m],
+        rpe_tra_sq [m] (NaN for an unused pose or edge)."""
+        d = self.d
+        X = np.asarray(X, dtype=np.float64)
+        flat = np.ascontiguousarray(X.T).ravel() if X.ndim == 2 else np.ascontiguousarray(X).ravel()
+        if flat.size != r * (d + 1) * self.n:
+            raise DPGOHipError("X has the wrong size")
+        t, nt = _traj_flat(T_truth, d, "T_truth")
+        if nt != self.n:
+            raise DPGOHipError("T_truth must have one pose per pose of the graph")
+        u = None
+        if use is not None:
+            u, _ = _i32(use)
+            if u.size != self.n:
+                raise DPGOHipError("use must have one entry per pose")
+        if align not in EVAL_ALIGN:
+            raise DPGOHipError(f"evaluate: unknown align {align!r}")
+        info = EvalInfo()
+        arr = {}
+        if per_item:
+            arr = dict(tra_sq=np.empty(self.n), rot_sq=np.empty(self.n), rpe_rot_sq=np.empty(max(self.m, 1)),
+                       rpe_tra_sq=np.empty(max(self.m, 1)))
+        _check(lib().dpgo_graph_evaluate(self.h, int(r), flat.ctypes.data_as(_dp), t.ctypes.data_as(_dp),
+                                         _opt_ptr(u, _ip), EVAL_ALIGN[align], int(pose), C.byref(info),
+                                         *[_opt_ptr(arr.get(k)) for k in ("tra_sq", "rot_sq", "rpe_rot_sq",
+                                                                          "rpe_tra_sq")]))
+        out = {k: getattr(info, k) for k, _ in EvalInfo._fields_ if k not in ("Aa", "sigma")}
+        out["Aa"] = np.array(info.Aa[:d * (d + 1)]).reshape(d + 1, d).T.copy()
+        out["sigma"] = np.array(info.sigma[:d])
+        for k, v in arr.items():
+            out[k] = v[:self.m] if k.startswith("rpe") else v
+        return out
+
     def grid_partition(self, agents_per_axis):
         out = np.empty(self.n, np.int32)
         _check(lib().dpgo_graph_grid_partition(self.h, int(agents_per_axis), out.ctypes.data_as(_ip)))
@@ -1498,6 +1766,73 @@ class Rbcd:
             if a.size != self.params.r * (self.graph.d + 1):
                 raise ValueError("anchor must be r x (d+1)")
         _check(lib().dpgo_rbcd_get_trajectory(self.h, ap, T_flat.ctypes.data_as(_dp)))
+
+    def _anchor_ptr(self, anchor):
+        if anchor is None:
+            return None, None
+        a, ap = _f64(to_dev_layout(anchor))
+        if a.size != self.params.r * (self.graph.d + 1):
+            raise ValueError("anchor must be r x (d+1)")
+        return a, ap
+
+    def set_truth(self, T_truth, use=None):
+        """The ground truth (d x (d+1) n matrix or flat buffer, global pose order) and mask (one int per global pose,
+        None = every pose) the truth_* calls compare against: the owned poses' part goes to the device once.
+        T_truth None clears it."""
+        if T_truth is None:
+            _check(lib().dpgo_rbcd_set_truth(self.h, None, None))
+            return
+        d = self.graph.d
+        t, n = _traj_flat(T_truth, d, "T_truth")
+        if n != self.graph.n:
+            raise ValueError("T_truth must have one pose per pose of the graph")
+        u = None
+        if use is not None:
+            u, _ = _i32(use)
+            if u.size != n:
+                raise ValueError("use must have one entry per pose")
+        _check(lib().dpgo_rbcd_set_truth(self.h, t.ctypes.data_as(_dp), _opt_ptr(u, _ip)))
+
+    def truth_moments(self, anchor=None, shift=None):
+        """This rank's traj_moments vector of its owned poses (rounded on the device in the frame of `anchor`, as
+        trajectory_into) against their truth, about shift (2 d, None = zeros); with several ranks the caller sums."""
+        d = self.graph.d
+        a, ap = self._anchor_ptr(anchor)
+        s = _opt_vec(shift, 2 * d, "shift")
+        mom = np.empty(traj_moments_len(d))
+        _check(lib().dpgo_rbcd_truth_moments(self.h, ap, _opt_ptr(s), mom.ctypes.data_as(_dp)))
+        return mom
+
+    def truth_errors(self, anchor=None, Aa=None, tra_sq=None, rot_sq=None, sums=True):
+        """traj_errors of the owned poses under Aa (d x (d+1), None = identity): tra_sq / rot_sq (global arrays of n
+        doubles, each optional) are written at the owned poses, other entries untouched; returns this rank's partial
+        sums (merge_traj_sums joins the ranks') or None."""
+        a, ap = self._anchor_ptr(anchor)
+        A = _aa_colmajor(Aa, self.graph.d)
+        for x in (tra_sq, rot_sq):
+            if x is not None:
+                assert x.dtype == np.float64 and x.flags.c_contiguous
+                if x.size < self.graph.n:
+                    raise ValueError(f"the array holds {x.size} doubles, the graph has {self.graph.n} poses")
+        s = np.empty(TRAJ_SUMS) if sums else None
+        _check(lib().dpgo_rbcd_truth_errors(self.h, ap, _opt_ptr(A), _opt_ptr(tra_sq), _opt_ptr(rot_sq), _opt_ptr(s)))
+        return s
+
+    def evaluate(self, anchor=None):
+        """ATE of the engine's solution against set_truth's trajectory for world = 1: two truth_moments calls (the
+        means, then about them), align_moments, truth_errors.  dict(count, Aa, sigma, rank, ate_rmse, ate_max,
+        rot_rmse, rot_max, tra_sq [n], rot_sq [n]).  (The RPE is Graph.evaluate's, of trajectory_into's T.)"""
+        d, n = self.graph.d, self.graph.n
+        m0 = self.truth_moments(anchor)
+        if not m0[0] >= 1:
+            raise DPGOHipError("evaluate: no pose counted")
+        shift = m0[3:3 + 2 * d] / m0[0]
+        Aa, info = align_moments(d, self.truth_moments(anchor, shift), shift)
+        tra, rot = np.full(n, np.nan), np.full(n, np.nan)
+        s = self.truth_errors(anchor, Aa, tra, rot)
+        return dict(count=s[0], Aa=Aa, sigma=info["sigma"], rank=info["rank"], ate_rmse=float(np.sqrt(s[1] / s[0])),
+                    ate_max=float(np.sqrt(s[3])), rot_rmse=float(np.sqrt(s[2] / s[0])), rot_max=float(np.sqrt(s[4])),
+                    tra_sq=tra, rot_sq=rot)
 
     def gram(self):
         """This rank's partial Gram sum_j Y_j Y_j^T (r x r) over its owned poses, from the engine's X on the device;

@@ -455,6 +455,75 @@ int dpgo_hip_edge_errors_dev(int r, int d, long long n, const dpgo_edges* E_dev,
                              double* err_dev, double* rot_sq_dev, double* tra_sq_dev,
                              double* cost_dev, double* work_dev, void* stream);
 
+/* ---- trajectory evaluation against a ground truth: alignment, ATE, RPE (build-defined; the reference has none:
+ * pinned against a long double restatement) -----------------------------------------------------------------
+ * A trajectory is d x (d+1) n doubles column-major, the layout dpgo_hip_round_se writes: pose j is d (d+1)
+ * contiguous doubles [R_j (d x d column-major) | t_j].  That is the estimate, T the truth, d in {2, 3}.  `use` has
+ * one int per pose: NULL = every pose, otherwise pose j counts iff use[j] != 0.
+ *
+ * Moments.  With a shift (s^, s) (2 d doubles, host memory, NULL = zeros), a_j = fl(t^_j - s^), b_j = fl(t_j - s):
+ *   mom = [count, sum |a|^2, sum |b|^2, sum a (d), sum b (d), M = sum b a^T (d x d column-major)]
+ * over the used poses, DPGO_TRAJ_MOMENTS(d) doubles.  Every entry is additive over disjoint pose sets: ranks merge
+ * by summation.  One streaming kernel that leaves one partial per 128 poses and one finishing launch that sums them
+ * in a fixed order, no atomics: mom is a function of the inputs alone, bitwise repeatable, and bitwise the same for
+ * any 8-byte alignment of the pointers.
+ *
+ * Alignment from moments (host, no device needed).  n = count, mu^ = s^ + sum a / n, mu = s + sum b / n,
+ * C = M - (sum b)(sum a)^T / n = U Sigma V^T (one-sided Jacobi), A = U diag(1, .., 1, det(U V^T)) V^T,
+ * a = mu - A mu^: Horn / Umeyama without scale on the translations, the minimiser of sum |A t^_j + a - t_j|^2 over
+ * SE(d).  Aa = [A | a], d x (d+1) column-major.  info: count, sigma descending with the d-th signed by that
+ * determinant, rank = #{sigma_i > rank_tol sigma_1} (rank_tol <= 0 = the default 1e-12).  A is unique iff
+ * rank >= d - 1; it is returned either way (C = 0, one pose: A = I).  count = 0 is DPGO_HIP_EINVAL.
+ * dpgo_hip_traj_align takes the moments twice -- with a zero shift for the means, then about those means, where C's
+ * correction term is at rounding level however far the trajectory lies from the origin -- and aligns: one upload,
+ * two launches, one host step.  At several ranks the caller sums the moment vectors between the two.
+ *
+ * Errors.  Given Aa (host memory, NULL = identity), per pose
+ *   tra_sq[j] = |A t^_j + a - t_j|^2,   rot_sq[j] = |A R^_j - R_j|_F^2   (chordal; the angle is
+ *   2 asin(min(1, sqrt(rot_sq / 8)))),
+ * a quiet NaN for an unused pose; sums (DPGO_TRAJ_SUMS doubles) = [count, sum tra_sq, sum rot_sq, max tra_sq,
+ * max rot_sq] over the used poses: ATE RMSE = sqrt(sums[1] / sums[0]).  A pose's outputs depend on its own data and
+ * Aa alone, through one operation order per d; the sums go through block partials in a fixed order and the maxima
+ * are exact.  Any of tra_sq, rot_sq, sums may be NULL, not all three.  Ranks merge sums by adding entries 0-2 and
+ * taking the maximum of 3-4.
+ *
+ * Relative poses of a trajectory over an edge list (p1, p2), as dpgo_edges takes measurements:
+ *   R_out[e] (d d row-major) = R_p1^T R_p2,   t_out[e] = R_p1^T (t_p2 - t_p1).
+ * RPE is dpgo_hip_edge_errors at r = d on the estimate with the truth's relative poses as the measurements and
+ * kappa = tau = 1: its rot_sq and tra_sq per edge are gauge-free, no alignment enters.
+ *
+ * DPGO_HIP_EINVAL for d outside {2, 3}, n <= 0 (m <= 0), a null required pointer, an output overlapping an input
+ * or another output and, on the host-pointer entries, p1 == p2 or an index outside [0, n); the outputs are then
+ * untouched.  The _dev entries take device pointers (shift and Aa stay host memory), queue on `stream`
+ * (hipStream_t or NULL) without synchronisation, trust the indices, and take their block partials from the caller
+ * (work_dev, the *_work_doubles query; it must not overlap anything else). */
+#define DPGO_TRAJ_MOMENTS(d) (3 + 2 * (d) + (d) * (d))
+#define DPGO_TRAJ_SUMS 5
+typedef struct {
+  double count;     /* used poses */
+  double sigma[3];  /* singular values of C, descending; the d-th carries the sign of det(U V^T) */
+  int rank;         /* #{i : sigma_i > rank_tol sigma_1} (0 for C = 0) */
+} dpgo_align_info;
+int dpgo_hip_traj_moments(int d, int n, const double* That, const double* T, const int* use, const double* shift,
+                          double* mom);
+long long dpgo_hip_traj_moments_work_doubles(int d, long long n);
+int dpgo_hip_traj_moments_dev(int d, long long n, const double* That_dev, const double* T_dev, const int* use_dev,
+                              const double* shift, double* mom_dev, double* work_dev, void* stream);
+int dpgo_hip_align_moments(int d, const double* shift, const double* mom, double rank_tol, double* Aa,
+                           dpgo_align_info* info);
+int dpgo_hip_traj_align(int d, int n, const double* That, const double* T, const int* use, double* Aa,
+                        dpgo_align_info* info);
+int dpgo_hip_traj_errors(int d, int n, const double* That, const double* T, const int* use, const double* Aa,
+                         double* tra_sq, double* rot_sq, double* sums);
+long long dpgo_hip_traj_errors_work_doubles(int d, long long n);
+int dpgo_hip_traj_errors_dev(int d, long long n, const double* That_dev, const double* T_dev, const int* use_dev,
+                             const double* Aa, double* tra_sq_dev, double* rot_sq_dev, double* sums_dev,
+                             double* work_dev, void* stream);
+int dpgo_hip_relative_poses(int d, int n, const double* T, int m, const int* p1, const int* p2, double* R_out,
+                            double* t_out);
+int dpgo_hip_relative_poses_dev(int d, long long n, const double* T_dev, long long m, const int* p1_dev,
+                                const int* p2_dev, double* R_out_dev, double* t_out_dev, void* stream);
+
 /* ---- measurement helpers ----------------------------------------------------------------*/
 /* Select a compiled kernel variant / host sequence for A/B timing (process-wide; every setting gives
  * results within the documented bars, most bitwise the default's).  key 0: BSR X.Q SpMM

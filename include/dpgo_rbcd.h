@@ -184,6 +184,47 @@ int dpgo_graph_edge_errors(dpgo_graph g, int r, const double* X, const double* w
                            double* err, double* rot_sq, double* tra_sq, double* cost);
 int dpgo_graph_grid_partition(dpgo_graph g, int agents_per_axis, int* agent_of_pose);
 
+/* ---- evaluation against a ground truth (build-defined; dpgo_hip_traj_* in include/dpgo_hip.h) ----
+ * The poses dpgo_graph_grid3d(k, seed, ..) measured: rotation i from the first 4 n normals of the seed's stream, the
+ * translation its lattice coordinates.  T_out: 3 x 4 n column-major, 12 doubles per pose [R_i | t_i]; bitwise the
+ * oracle's grid3d(...).extra["ground_truth"].  Host only.  DPGO_HIP_EINVAL for k outside [2, 200] or a null T_out. */
+int dpgo_graph_grid3d_truth(int k, unsigned long long seed, double* T_out);
+/* The VERTEX_SE2 (id x y theta) and VERTEX_SE3:QUAT (id x y z qx qy qz qw) lines of a g2o file as a reference
+ * trajectory of n poses, T_out d x (d+1) n column-major (the id's low 48 bits index the pose, as for the edges).
+ * The quaternion is normalised before it becomes a rotation -- unlike the edge reader's, which keeps the
+ * reference's unnormalised Eigen conversion -- because a reference pose must be a rotation.  present (n ints, may
+ * be NULL) is 1 for the ids the file gave; an absent pose has present = 0 and NaN in all its d (d+1) entries (a
+ * later line of the same id replaces an earlier one).  Host only.  DPGO_HIP_EINVAL for an unreadable file, d
+ * outside {2, 3}, n <= 0, a vertex line of the other dimension, a zero quaternion, or an id >= n; the outputs are
+ * then untouched. */
+int dpgo_g2o_read_vertices(const char* path, int d, int n, double* T_out, int* present);
+#define DPGO_ALIGN_NONE 0 /* compare as given */
+#define DPGO_ALIGN_POSE 1 /* A = R_p R^_p^T, a = t_p - A t^_p of the pose `pose` */
+#define DPGO_ALIGN_LSQ 2  /* dpgo_hip_traj_align over the used poses */
+typedef struct {
+  double count;        /* used poses */
+  double Aa[12];       /* [A | a], d x (d+1) column-major */
+  double sigma[3];     /* dpgo_align_info's (NaN unless DPGO_ALIGN_LSQ) */
+  int rank;            /* dpgo_align_info's (-1 unless DPGO_ALIGN_LSQ) */
+  double ate_rmse, ate_max;  /* sqrt(mean tra_sq), sqrt(max tra_sq) over the used poses */
+  double rot_rmse, rot_max;  /* the same of the chordal rot_sq */
+  double rpe_tra_rmse, rpe_rot_rmse;  /* sqrt(mean) of the RPE residuals over the edges used */
+  double edges_used;   /* edges with both endpoints used */
+} dpgo_eval_info;
+/* A solution X (r x (d+1) n column-major, any compiled r >= d) of the graph against the truth T_truth
+ * (d x (d+1) n), everything on the device after one upload: r > d is rounded by dpgo_hip_round_se_dev in the frame
+ * of X's pose `pose` (r = d is taken as it is), aligned as `align` says, dpgo_hip_traj_errors_dev gives tra_sq and
+ * rot_sq per pose (n each), dpgo_hip_relative_poses_dev the truth's relative poses over the graph's own edges, and
+ * dpgo_hip_edge_errors_dev at r = d with kappa = tau = 1 the RPE residuals rpe_rot_sq and rpe_tra_sq per edge (m
+ * each).  The RPE means are that kernel's cost with (kappa, tau) = (1, 0) and (0, 1) over the edges whose
+ * endpoints are both used: deterministic.  The other edges are left out of the launch (as if they had weight 0,
+ * but a truth that is NaN at its unused poses cannot reach the sums) and get NaN per edge.  use as in
+ * dpgo_hip_traj_errors; every per-item array may be NULL.  DPGO_HIP_EINVAL for a null g, X, T_truth or info, an
+ * unsupported r, an unknown align, pose outside [0, n), or DPGO_ALIGN_POSE on an unused pose. */
+int dpgo_graph_evaluate(dpgo_graph g, int r, const double* X, const double* T_truth, const int* use, int align,
+                        int pose, dpgo_eval_info* info, double* tra_sq, double* rot_sq, double* rpe_rot_sq,
+                        double* rpe_tra_sq);
+
 /* ---- RBCD engine ----------------------------------------------------------------------------*/
 typedef struct {
   int r;                  /* relaxation rank */
@@ -262,6 +303,27 @@ int dpgo_rbcd_get_anchor(dpgo_rbcd e, int pose, double* anchor, int* owned);
  * of a global d x (d+1) n column-major host array (other poses untouched, as get_X).  Only the rounded
  * poses cross to the host.  Synchronises. */
 int dpgo_rbcd_get_trajectory(dpgo_rbcd e, const double* anchor, double* T_global);
+/* ---- the engine's trajectory against a ground truth (dpgo_hip_traj_*, include/dpgo_hip.h): the rounded
+ * trajectory never leaves the device and nothing is gathered ------------------------------------------------
+ * The truth of the owned poses (from a global d x (d+1) n column-major host array) and their mask (use_global: one
+ * int per global pose, NULL = every pose) go to the device once, in the engine's pose order.  T_truth_global NULL
+ * clears it.  Synchronises. */
+int dpgo_rbcd_set_truth(dpgo_rbcd e, const double* T_truth_global, const int* use_global);
+/* This rank's moments (DPGO_TRAJ_MOMENTS(d) doubles) of its owned poses, rounded into engine scratch in the frame
+ * of `anchor` with the conventions and refusals of dpgo_rbcd_get_trajectory, against their truth about `shift`
+ * (2 d doubles, NULL = zeros): one rounding and one dpgo_hip_traj_moments_dev on the engine's stream; only the
+ * moments cross to the host.  With several ranks the caller sums the vectors (a valid moment vector within the
+ * rounding bound, not bitwise the one-rank value, as for dpgo_rbcd_gram), takes the means from the zero-shift call
+ * as the shift of a second one, and gives that sum to dpgo_hip_align_moments.  A rank without poses writes zeros.
+ * DPGO_HIP_EINVAL before dpgo_rbcd_set_truth.  Synchronises. */
+int dpgo_rbcd_truth_moments(dpgo_rbcd e, const double* anchor, const double* shift, double* mom);
+/* dpgo_hip_traj_errors_dev of the same rounded poses under Aa ([A | a], NULL = identity): tra_sq and rot_sq land
+ * at the owned poses of global arrays of n doubles (other entries untouched, as get_X; each may be NULL), bitwise
+ * dpgo_hip_traj_errors of the merged dpgo_rbcd_get_trajectory.  sums (DPGO_TRAJ_SUMS doubles, may be NULL) is this
+ * rank's partial: the caller adds entries 0-2 over the ranks and takes the maximum of 3-4.  A rank without poses
+ * writes zero sums.  DPGO_HIP_EINVAL before dpgo_rbcd_set_truth or with no output.  Synchronises. */
+int dpgo_rbcd_truth_errors(dpgo_rbcd e, const double* anchor, const double* Aa, double* tra_sq_global,
+                           double* rot_sq_global, double* sums);
 /* ---- rank reduction on the engine's X (dpgo_hip_gram / dpgo_hip_rank_reduce, include/dpgo_hip.h) ------
  * This rank's partial Gram C (r x r, column-major) = sum over its owned poses of Y_j Y_j^T: the owned buffer is
  * contiguous, so one dpgo_hip_gram_dev on the engine's stream, and 8 r^2 bytes cross to the host.  Synchronises.  With
