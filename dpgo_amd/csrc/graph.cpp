@@ -555,6 +555,33 @@ void dpgo_default_init_params(dpgo_init_params* p) {
   p->use_gpu = 0;
   p->rtol = 1e-12;
   p->max_iters = 20000;
+  p->max_translation_error = 0.0;  // unset: PCM refuses until the caller gives one
+  p->clique_node_budget = 10000000;
+}
+
+static int check_pcm_params(const dpgo_init_params& P) {
+  if (!(P.max_translation_error > 0.0))
+    return fail(DPGO_HIP_EINVAL, "pairwise consistency needs max_translation_error (c_t) > 0: it is unset by default");
+  if (!(P.max_rotation_error > 0.0)) return fail(DPGO_HIP_EINVAL, "pairwise consistency needs max_rotation_error > 0");
+  return DPGO_HIP_OK;
+}
+
+int dpgo_graph_pcm(dpgo_graph g, int num_agents, const int* agent_of_pose, const double* T_local,
+                   const dpgo_init_params* params, unsigned char* edge_inlier, dpgo_pcm_info* info) {
+  if (!g || !agent_of_pose || num_agents <= 0 || !T_local || !edge_inlier)
+    return fail(DPGO_HIP_EINVAL, "pcm: null argument");
+  dpgo_init_params P;
+  dpgo_default_init_params(&P);
+  if (params) P = *params;
+  DPGO_TRY(check_pcm_params(P));
+  for (int i = 0; i < g->n; ++i)
+    if (agent_of_pose[i] < 0 || agent_of_pose[i] >= num_agents) return fail(DPGO_HIP_EINVAL, "agent_of_pose out of range");
+  if (P.use_gpu && usable_devices() == 0) return fail(DPGO_HIP_ENODEV, "no gfx950 device available (no CPU fallback)");
+  std::string err;
+  if (dpgo::graph_pcm(g->d, g->n, static_cast<int>(g->p1.size()), g->p1.data(), g->p2.data(), g->R.data(),
+                      g->t.data(), agent_of_pose, num_agents, T_local, P, edge_inlier, info, err) != 0)
+    return fail(P.use_gpu ? DPGO_HIP_EDEVICE : DPGO_HIP_EINVAL, err);
+  return DPGO_HIP_OK;
 }
 
 int dpgo_graph_distributed_init_ex(dpgo_graph g, int num_agents, const int* agent_of_pose,
@@ -567,14 +594,17 @@ int dpgo_graph_distributed_init_ex(dpgo_graph g, int num_agents, const int* agen
   dpgo_default_init_params(&P);
   if (params) P = *params;
   if ((P.local_init != DPGO_LOCAL_CHORDAL && P.local_init != DPGO_LOCAL_ODOMETRY) ||
-      (P.align != DPGO_ALIGN_L2 && P.align != DPGO_ALIGN_ROBUST_TWO_STAGE))
+      (P.align != DPGO_ALIGN_L2 && P.align != DPGO_ALIGN_ROBUST_TWO_STAGE && P.align != DPGO_ALIGN_PCM))
     return fail(DPGO_HIP_EINVAL, "unknown local_init or align");
   for (int i = 0; i < g->n; ++i)
     if (agent_of_pose[i] < 0 || agent_of_pose[i] >= num_agents) return fail(DPGO_HIP_EINVAL, "agent_of_pose out of range");
-  const bool gpu = P.use_gpu != 0 && P.local_init == DPGO_LOCAL_CHORDAL;  // only the chordal solves can use the device
+  // the chordal solves and PCM's pair tests can use the device
+  const bool gpu = P.use_gpu != 0 && (P.local_init == DPGO_LOCAL_CHORDAL || P.align == DPGO_ALIGN_PCM);
   P.use_gpu = gpu ? 1 : 0;
   if (gpu && usable_devices() == 0) return fail(DPGO_HIP_ENODEV, "no gfx950 device available (no CPU fallback)");
-  if (gpu && (!(P.rtol > 0.0) || P.max_iters < 1)) return fail(DPGO_HIP_EINVAL, "bad PCG tolerance");
+  if (gpu && P.local_init == DPGO_LOCAL_CHORDAL && (!(P.rtol > 0.0) || P.max_iters < 1))
+    return fail(DPGO_HIP_EINVAL, "bad PCG tolerance");
+  if (P.align == DPGO_ALIGN_PCM) DPGO_TRY(check_pcm_params(P));
   if (P.align == DPGO_ALIGN_ROBUST_TWO_STAGE &&
       (!(P.max_rotation_error > 0.0) || P.gnc_max_iters < 0 || !(P.gnc_mu_step > 0.0)))
     return fail(DPGO_HIP_EINVAL, "bad GNC parameters");

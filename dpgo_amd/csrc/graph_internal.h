@@ -55,6 +55,10 @@ int distributed_initialization_ex(int d, int n, int m, const int* p1, const int*
                                   const dpgo_init_params& P, double* T_local, double* frames, int* parent,
                                   int* candidates, int* inliers, unsigned char* edge_inlier, int* iters, double* relres,
                                   std::string& err);
+// dpgo_graph_pcm (init.cpp): Tl d x (d+1) n column-major local trajectories; edge_inlier[m]
+int graph_pcm(int d, int n, int m, const int* p1, const int* p2, const double* R, const double* t, const int* agent_of,
+              int num_agents, const double* Tl, const dpgo_init_params& P, unsigned char* edge_inlier,
+              dpgo_pcm_info* info, std::string& err);
 int distributed_initialization(int d, int n, int m, const int* p1, const int* p2, const double* R, const double* t,
                                const double* kappa, const double* tau, const int* agent_of, int num_agents, bool gpu,
                                double rtol, int max_iters, double* T_out, int* iters, double* relres,

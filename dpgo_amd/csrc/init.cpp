@@ -707,7 +707,8 @@ int distributed_initialization_ex(int d, int n, int m, const int* p1, const int*
       tw[u] = s;
     }
   };
-  const bool robust = P.align == DPGO_ALIGN_ROBUST_TWO_STAGE;
+  const bool pcm = P.align == DPGO_ALIGN_PCM;
+  const bool robust = P.align == DPGO_ALIGN_ROBUST_TWO_STAGE || pcm;  // the single-parent candidates
   for (size_t h = 0; h < order.size(); ++h) {
     for (int A : nbr[order[h]]) {
       if (done[A]) continue;
@@ -765,6 +766,50 @@ int distributed_initialization_ex(int d, int n, int m, const int* p1, const int*
             for (int w = 0; w < d; ++w) s += Fi[u * d + w] * tl(est[x].p, w);
             ct[static_cast<size_t>(x) * d + u] = est[x].tw[u] - s;
           }
+        }
+        if (pcm) {
+          // the candidates as one group of the pair test (lever: the child's closure pose in its local frame), the
+          // maximum clique as the inlier set; rotation: ALIGN_L2's chordal mean (unit weights) over the clique in
+          // candidate order, projected; translation: the clique's plain mean
+          std::vector<double> Fc(static_cast<size_t>(nc) * d * b), xc(static_cast<size_t>(nc) * d);
+          for (int x = 0; x < nc; ++x)
+            for (int u = 0; u < d; ++u) {
+              for (int c = 0; c < d; ++c) Fc[(static_cast<size_t>(x) * b + c) * d + u] = cR[static_cast<size_t>(x) * d2 + u * d + c];
+              Fc[(static_cast<size_t>(x) * b + d) * d + u] = ct[static_cast<size_t>(x) * d + u];
+              xc[static_cast<size_t>(x) * d + u] = tl(est[x].p, u);
+            }
+          const int goff[2] = {0, nc}, words = (nc + 63) / 64;
+          std::vector<unsigned long long> adj(static_cast<size_t>(nc) * words);
+          std::vector<int> deg(nc), clique(nc);
+          int size = 0, proven = 0;
+          const int rc = gpu ? dpgo_hip_pair_consistency(d, nc, Fc.data(), xc.data(), 1, goff, P.max_rotation_error,
+                                                         P.max_translation_error, adj.data(),
+                                                         static_cast<long long>(adj.size()), deg.data(), nullptr, nullptr)
+                             : dpgo_pair_consistency_host(d, nc, Fc.data(), xc.data(), 1, goff, P.max_rotation_error,
+                                                          P.max_translation_error, adj.data(),
+                                                          static_cast<long long>(adj.size()), deg.data(), nullptr,
+                                                          nullptr);
+          if (rc != 0 || dpgo_max_clique(nc, words, adj.data(), P.clique_node_budget, clique.data(), &size, &proven) != 0) {
+            err = dpgo_hip_last_error();
+            return -1;
+          }
+          if (edge_inlier)
+            for (int x = 0; x < nc; ++x) edge_inlier[est[x].e] = 0;
+          double M[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, tsum[3] = {0, 0, 0};
+          for (int q = 0; q < size; ++q) {
+            const int x = clique[q];
+            if (edge_inlier) edge_inlier[est[x].e] = 1;
+            for (int y = 0; y < d2; ++y) M[y] += cR[static_cast<size_t>(x) * d2 + y];
+            for (int u = 0; u < d; ++u) tsum[u] += ct[static_cast<size_t>(x) * d + u];
+          }
+          project_rotation(d, M, F);
+          for (int u = 0; u < d; ++u) Ft[static_cast<size_t>(A) * d + u] = tsum[u] / size;
+          inliers[A] = size;  // >= 1: a group of nc >= 1 candidates has a clique of at least one
+          parent[A] = order[h];
+          candidates[A] = nc;
+          done[A] = 1;
+          order.push_back(A);
+          continue;
         }
         double Fopt[9];
         if (robust_rotation_average(d, nc, cR.data(), nullptr, P.max_rotation_error, P.gnc_max_iters, P.gnc_mu_step,
@@ -830,6 +875,107 @@ int distributed_initialization_ex(int d, int n, int m, const int* p1, const int*
       F[d * d + u] = Ft[static_cast<size_t>(a) * d + u];
     }
   }
+  return 0;
+}
+
+// dpgo_graph_pcm: every unordered agent pair with shared closures is one group; all groups go through one call of
+// the pair test, then one clique search per group.
+int graph_pcm(int d, int n, int m, const int* p1, const int* p2, const double* R, const double* t, const int* agent_of,
+              int num_agents, const double* Tl, const dpgo_init_params& P, unsigned char* edge_inlier,
+              dpgo_pcm_info* info, std::string& err) {
+  const int d2 = d * d, b = d + 1;
+  (void)n;
+  (void)num_agents;
+  std::map<std::pair<int, int>, std::vector<int>> groups;  // ordered: (A, B) ascending, edges in graph order
+  for (int e = 0; e < m; ++e) {
+    const int ai = agent_of[p1[e]], aj = agent_of[p2[e]];
+    edge_inlier[e] = 255;
+    if (ai != aj) groups[{std::min(ai, aj), std::max(ai, aj)}].push_back(e);
+  }
+  std::vector<int> goff{0}, edge_of;
+  for (const auto& kv : groups) {
+    edge_of.insert(edge_of.end(), kv.second.begin(), kv.second.end());
+    goff.push_back(static_cast<int>(edge_of.size()));
+  }
+  const int ng = static_cast<int>(groups.size()), mc = static_cast<int>(edge_of.size());
+  auto Rl = [&](int p, int u, int c) { return Tl[(static_cast<size_t>(p) * b + c) * d + u]; };
+  auto tl = [&](int p, int u) { return Tl[(static_cast<size_t>(p) * b + d) * d + u]; };
+  std::vector<double> Fc(static_cast<size_t>(mc) * d * b), xc(static_cast<size_t>(mc) * d);
+  for (int k = 0; k < mc; ++k) {
+    const int e = edge_of[k], i = p1[e], j = p2[e];
+    const bool fwd = agent_of[i] < agent_of[j];  // the edge leaves A; else it leaves B and Z is inverted
+    const int pa = fwd ? i : j, pb = fwd ? j : i;
+    const double* Re = R + static_cast<size_t>(e) * d2;
+    const double* te = t + static_cast<size_t>(e) * d;
+    double Zr[9], Zt[3], Wr[9], Wt[3], Fr[9];
+    for (int u = 0; u < d; ++u) {  // Z or Z^-1 = [R^T | -R^T t]
+      for (int c = 0; c < d; ++c) Zr[u * d + c] = fwd ? Re[u * d + c] : Re[c * d + u];
+      double s = 0.0;
+      for (int w = 0; w < d; ++w) s += Re[w * d + u] * te[w];
+      Zt[u] = fwd ? te[u] : -s;
+    }
+    for (int u = 0; u < d; ++u) {  // W = T_a Z
+      for (int c = 0; c < d; ++c) {
+        double s = 0.0;
+        for (int w = 0; w < d; ++w) s += Rl(pa, u, w) * Zr[w * d + c];
+        Wr[u * d + c] = s;
+      }
+      double s = tl(pa, u);
+      for (int w = 0; w < d; ++w) s += Rl(pa, u, w) * Zt[w];
+      Wt[u] = s;
+    }
+    for (int u = 0; u < d; ++u) {  // F = W T_b^-1 = [W_R R_b^T | W_t - W_R R_b^T t_b]
+      for (int c = 0; c < d; ++c) {
+        double s = 0.0;
+        for (int w = 0; w < d; ++w) s += Wr[u * d + w] * Rl(pb, c, w);
+        Fr[u * d + c] = s;
+      }
+    }
+    for (int u = 0; u < d; ++u) {
+      double s = 0.0;
+      for (int w = 0; w < d; ++w) s += Fr[u * d + w] * tl(pb, w);
+      for (int c = 0; c < d; ++c) Fc[(static_cast<size_t>(k) * b + c) * d + u] = Fr[u * d + c];
+      Fc[(static_cast<size_t>(k) * b + d) * d + u] = Wt[u] - s;
+      xc[static_cast<size_t>(k) * d + u] = tl(pb, u);
+    }
+  }
+  std::vector<long long> woff(static_cast<size_t>(ng) + 1, 0);
+  if (dpgo_hip_pair_consistency_words(ng, goff.data(), woff.data(), -1) != 0) {
+    err = dpgo_hip_last_error();
+    return -1;
+  }
+  std::vector<unsigned long long> adj(static_cast<size_t>(woff[ng]));
+  std::vector<int> deg(mc), clique;
+  const int rc = P.use_gpu ? dpgo_hip_pair_consistency(d, mc, Fc.data(), xc.data(), ng, goff.data(), P.max_rotation_error,
+                                                       P.max_translation_error, adj.data(), woff[ng], deg.data(),
+                                                       nullptr, nullptr)
+                           : dpgo_pair_consistency_host(d, mc, Fc.data(), xc.data(), ng, goff.data(),
+                                                        P.max_rotation_error, P.max_translation_error, adj.data(),
+                                                        woff[ng], deg.data(), nullptr, nullptr);
+  if (rc != 0) {
+    err = dpgo_hip_last_error();
+    return -1;
+  }
+  dpgo_pcm_info I{};
+  I.groups = ng;
+  I.candidates = mc;
+  I.min_clique_ratio = 1.0;
+  for (int g = 0; g < ng; ++g) {
+    const int mg = goff[g + 1] - goff[g], words = (mg + 63) / 64;
+    clique.resize(mg);
+    int size = 0, proven = 0;
+    if (dpgo_max_clique(mg, words, adj.data() + woff[g], P.clique_node_budget, clique.data(), &size, &proven) != 0) {
+      err = dpgo_hip_last_error();
+      return -1;
+    }
+    for (int k = 0; k < mg; ++k) edge_inlier[edge_of[goff[g] + k]] = 0;
+    for (int q = 0; q < size; ++q) edge_inlier[edge_of[goff[g] + clique[q]]] = 1;
+    I.pair_tests += static_cast<long long>(mg) * mg;
+    I.inliers += size;
+    I.min_clique_ratio = std::min(I.min_clique_ratio, static_cast<double>(size) / mg);
+    if (!proven) ++I.unproven;
+  }
+  if (info) *info = I;
   return 0;
 }
 

@@ -516,6 +516,20 @@ hipError_t launch_traj_errors(int d, long n, const double* That, const double* T
 // R_out[e] (d d row-major) = R_p1^T R_p2, t_out[e] = R_p1^T (t_p2 - t_p1) over m edges of T; indices trusted
 hipError_t launch_relative_poses(int d, long m, const int* p1, const int* p2, const double* T, double* R_out,
                                  double* t_out, hipStream_t stream);
+// Pairwise consistency of frame candidates (build-defined; definitions and operation
+// order in pcm_pair.h).  One launch over `ntiles` 64 x 64 tiles of a host-built table (tiles[t] = (group, row tile,
+// column tile)); records: m candidates of pcm_record<d>() doubles split over F (d (d+1) each) and x (d each);
+// group_off / word_off / dense_off: ngroups + 1 offsets of each group's candidates, adjacency words and dense
+// entries.  One wave per tile: lane l keeps column candidate l in registers, the row candidates are read from LDS
+// at one address per step (a broadcast), __ballot of the 64 decisions is the row's word.  degree (m ints) is zeroed
+// on the stream ahead of the kernel and gathers the words' popcounts by integer atomics; e_rot / e_tra may be null.
+struct PcmTile {
+  int group, row_tile, col_tile;
+};
+hipError_t launch_pair_consistency(int d, long ntiles, const PcmTile* tiles, const double* F, const double* x,
+                                   const int* group_off, const long long* word_off, const long long* dense_off,
+                                   double cR2, double ct2, unsigned long long* adj, int* degree, int m,
+                                   double* e_rot, double* e_tra, hipStream_t stream);
 // PGOAgent::computeConvergedLoopClosureRatio (src/PGOAgent.cpp:1247-1289): per agent a, the share of
 // its loop closures idx[off[a] .. off[a+1]) whose weight w[] is exactly 1 or 0 (0/0 = NaN, as there)
 hipError_t launch_conv_ratio(int num_agents, const int* off, const int* idx, const double* w, double* ratio,

@@ -14,6 +14,7 @@
 
 #include "dpgo_device.h"
 #include "kernels.h"
+#include "pcm_pair.h"
 
 namespace dpgo {
 
@@ -3457,6 +3458,69 @@ __global__ __launch_bounds__(kEdgeErrThreads) void k_relative_poses(long m, cons
   }
 }
 
+// Pairwise consistency of frame candidates (pcm_pair.h: definitions, operation order, contraction off).  One wave
+// per 64 x 64 tile of one group: the tile's row candidates are staged in LDS (coalesced copy, record stride
+// pcm_record<D>()), lane l keeps column candidate c0 + l in registers (15 doubles at D = 3, 8 at D = 2) and the wave
+// walks the rows, every lane reading the row's record at one LDS address (a broadcast: no bank conflict).  The
+// ballot of the 64 decisions is word col_tile of row k; lane r keeps row r's word and stores it after the walk, one
+// plain 8-byte vector store per row.  A lane past the group's end votes 0, which leaves the padding bits zero; rows
+// past the end are not walked.  degree gathers __popcll of the stored words by integer atomics (exact in any order).
+template <int D>
+__global__ __launch_bounds__(64) void k_pair_consistency(const PcmTile* __restrict__ tiles,
+                                                         const double* __restrict__ F, const double* __restrict__ x,
+                                                         const int* __restrict__ group_off,
+                                                         const long long* __restrict__ word_off,
+                                                         const long long* __restrict__ dense_off, double cR2,
+                                                         double ct2, unsigned long long* __restrict__ adj,
+                                                         int* __restrict__ degree, double* __restrict__ e_rot,
+                                                         double* __restrict__ e_tra) {
+  constexpr int PW = D * (D + 1), REC = pcm_record<D>();
+  __shared__ double sm[64 * REC];
+  const int lane = static_cast<int>(threadIdx.x);
+  const PcmTile T = tiles[blockIdx.x];
+  const int g0 = group_off[T.group], mg = group_off[T.group + 1] - g0;
+  const int r0 = T.row_tile * 64, c0 = T.col_tile * 64;
+  const int rows = mg - r0 < 64 ? mg - r0 : 64;  // >= 1: the table lists tiles inside the group only
+  const double* Fr = F + static_cast<long>(g0 + r0) * PW;
+  const double* xr = x + static_cast<long>(g0 + r0) * D;
+  for (int i = lane; i < rows * PW; i += 64) sm[(i / PW) * REC + i % PW] = Fr[i];
+  for (int i = lane; i < rows * D; i += 64) sm[(i / D) * REC + PW + i % D] = xr[i];
+  const int l = c0 + lane;
+  const bool valid = l < mg;
+  double col[REC];
+#pragma unroll
+  for (int i = 0; i < REC; ++i) col[i] = 0.0;
+  if (valid) {
+    const double* Fc = F + static_cast<long>(g0 + l) * PW;
+    const double* xc = x + static_cast<long>(g0 + l) * D;
+#pragma unroll
+    for (int i = 0; i < PW; ++i) col[i] = Fc[i];
+#pragma unroll
+    for (int i = 0; i < D; ++i) col[PW + i] = xc[i];
+  }
+  __syncthreads();
+  const long long dbase = dense_off[T.group];
+  unsigned long long mine = 0;
+  for (int r = 0; r < rows; ++r) {
+    double er, et;
+    pcm_pair_errors<D>(sm + r * REC, col, er, et);
+    const int k = r0 + r;
+    const bool ok = valid && k != l && pcm_consistent(er, et, cR2, ct2);
+    const unsigned long long word = __ballot(ok);
+    if (lane == r) mine = word;
+    if (valid) {
+      const long long at = dbase + static_cast<long long>(k) * mg + l;
+      if (e_rot) e_rot[at] = er;
+      if (e_tra) e_tra[at] = et;
+    }
+  }
+  if (lane < rows) {
+    const int words = (mg + 63) / 64;
+    adj[word_off[T.group] + static_cast<long long>(r0 + lane) * words + T.col_tile] = mine;
+    if (mine != 0) atomicAdd(&degree[g0 + r0 + lane], __popcll(mine));
+  }
+}
+
 // Nesterov updateV deferred into the colour's next combination pass (one pass instead of two):
 //   V' = project(V + gv (X - Yv))   (updateV, src/PGOAgent.cpp:1086-1091, of the agent's last update)
 //   out = project(sa X + sb V')     (updateY / the iterate(false) step, :1077-1084, of the next iteration)
@@ -5931,6 +5995,26 @@ hipError_t launch_relative_poses(int d, long m, const int* p1, const int* p2, co
     k_relative_poses<2><<<grid, kEdgeErrThreads, 0, stream>>>(m, p1, p2, T, R_out, t_out);
   else
     k_relative_poses<3><<<grid, kEdgeErrThreads, 0, stream>>>(m, p1, p2, T, R_out, t_out);
+  return hipGetLastError();
+}
+
+hipError_t launch_pair_consistency(int d, long ntiles, const PcmTile* tiles, const double* F, const double* x,
+                                   const int* group_off, const long long* word_off, const long long* dense_off,
+                                   double cR2, double ct2, unsigned long long* adj, int* degree, int m,
+                                   double* e_rot, double* e_tra, hipStream_t stream) {
+  if ((d != 2 && d != 3) || ntiles < 0 || m < 0) return hipErrorInvalidValue;
+  if (m == 0) return hipSuccess;
+  if (!F || !x || !group_off || !word_off || !dense_off || !degree) return hipErrorInvalidValue;
+  const hipError_t z = hipMemsetAsync(degree, 0, sizeof(int) * static_cast<size_t>(m), stream);
+  if (z != hipSuccess || ntiles == 0) return z;
+  if (!tiles || !adj || ntiles > 0x7fffffffL) return hipErrorInvalidValue;
+  const dim3 grid(static_cast<unsigned>(ntiles));
+  if (d == 2)
+    k_pair_consistency<2><<<grid, 64, 0, stream>>>(tiles, F, x, group_off, word_off, dense_off, cR2, ct2, adj,
+                                                   degree, e_rot, e_tra);
+  else
+    k_pair_consistency<3><<<grid, 64, 0, stream>>>(tiles, F, x, group_off, word_off, dense_off, cR2, ct2, adj,
+                                                   degree, e_rot, e_tra);
   return hipGetLastError();
 }
 

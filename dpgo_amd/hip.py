@@ -1128,15 +1128,22 @@ class InitParams(C.Structure):
     """dpgo_init_params (include/dpgo_rbcd.h)."""
     _fields_ = [("local_init", C.c_int), ("align", C.c_int), ("max_rotation_error", C.c_double),
                 ("gnc_max_iters", C.c_int), ("gnc_mu_step", C.c_double), ("use_gpu", C.c_int), ("rtol", C.c_double),
-                ("max_iters", C.c_int)]
+                ("max_iters", C.c_int), ("max_translation_error", C.c_double), ("clique_node_budget", C.c_longlong)]
+
+
+class PcmInfo(C.Structure):
+    """dpgo_pcm_info (include/dpgo_rbcd.h)."""
+    _fields_ = [("groups", C.c_int), ("candidates", C.c_longlong), ("pair_tests", C.c_longlong),
+                ("inliers", C.c_longlong), ("min_clique_ratio", C.c_double), ("unproven", C.c_int)]
 
 
 LOCAL_INIT = {"chordal": 0, "odometry": 1}
-ALIGN = {"l2": 0, "robust": 1}
+ALIGN = {"l2": 0, "robust": 1, "pcm": 2}
 EVAL_ALIGN = {"none": 0, "pose": 1, "lsq": 2}  # DPGO_ALIGN_NONE / _POSE / _LSQ of dpgo_graph_evaluate
 _ubp = C.POINTER(C.c_ubyte)
 
 _lp = C.POINTER(C.c_longlong)
+_ullp = C.POINTER(C.c_ulonglong)
 _SIGS2 = [
     ("dpgo_graph_read_g2o", [C.c_char_p, C.POINTER(C.c_void_p)], C.c_int),
     ("dpgo_graph_grid3d", [C.c_int, C.c_ulonglong, C.c_double, C.c_double, C.POINTER(C.c_void_p)], C.c_int),
@@ -1182,6 +1189,18 @@ _SIGS2 = [
     ("dpgo_default_init_params", [C.POINTER(InitParams)], None),
     ("dpgo_graph_distributed_init_ex", [C.c_void_p, C.c_int, _ip, C.POINTER(InitParams), _dp, _dp, _ip, _ip, _ip, _ubp,
                                         _ip, _dp], C.c_int),
+    ("dpgo_graph_pcm", [C.c_void_p, C.c_int, _ip, _dp, C.POINTER(InitParams), _ubp, C.POINTER(PcmInfo)], C.c_int),
+    ("dpgo_hip_pair_consistency_words", [C.c_int, _ip, _lp, C.c_longlong], C.c_int),
+    ("dpgo_hip_pair_consistency", [C.c_int, C.c_int, _dp, _dp, C.c_int, _ip, C.c_double, C.c_double, _ullp,
+                                   C.c_longlong, _ip, _dp, _dp], C.c_int),
+    ("dpgo_hip_pair_consistency_dev", [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, _ip, C.c_double, C.c_double,
+                                       C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+     C.c_int),
+    ("dpgo_hip_pair_consistency_bench", [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, _ip, C.c_double, C.c_double,
+                                         C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_int, _dp], C.c_int),
+    ("dpgo_pair_consistency_host", [C.c_int, C.c_int, _dp, _dp, C.c_int, _ip, C.c_double, C.c_double, _ullp,
+                                    C.c_longlong, _ip, _dp, _dp], C.c_int),
+    ("dpgo_max_clique", [C.c_int, C.c_int, _ullp, C.c_longlong, _ip, _ip, _ip], C.c_int),
     ("dpgo_rbcd_default_params", [C.POINTER(RbcdParams)], None),
     ("dpgo_rbcd_plan", [C.c_void_p, C.c_int, _ip, _ip, C.c_int, C.c_int, _lp, _lp, _ip, _ip], C.c_int),
     ("dpgo_rbcd_create", [C.c_void_p, C.c_int, _ip, _ip, C.c_int, C.c_int, C.POINTER(RbcdParams),
@@ -1348,10 +1367,13 @@ class Graph:
         return (out if dev_layout else from_dev_layout(out, r)), it.value, rr.value
 
     def distributed_init_ex(self, agent_of_pose, local="chordal", align="l2", max_rotation_error=None,
-                            gnc_max_iters=None, gnc_mu_step=None, gpu=False, rtol=1e-12, max_iters=20000):
+                            gnc_max_iters=None, gnc_mu_step=None, gpu=False, rtol=1e-12, max_iters=20000,
+                            max_translation_error=None, clique_node_budget=None):
         """The multi-robot initialisation as local trajectories plus frames (dpgo_graph_distributed_init_ex):
         local "chordal" | "odometry" (what the reference does under a robust cost), align "l2" | "robust" (GNC-TLS
-        rotation averaging against the single breadth-first parent, translation mean over the inliers).  Returns
+        rotation averaging against the single breadth-first parent, translation mean over the inliers) | "pcm" (the
+        same parent and candidates, inliers = their maximum pairwise consistent set under max_rotation_error and
+        max_translation_error, which has no default; gpu then also selects the pair-test kernel).  Returns
         (T_local d x (d+1) n, frames K x d x (d+1), info dict(parent, candidates, inliers [K], edge_inlier [m]: 1 inlier
         candidate / 0 rejected / 255 unused, iters, relres)); Rbcd.set_trajectory and frame_lift take them as they
         are."""
@@ -1367,6 +1389,10 @@ class Graph:
         if gnc_mu_step is not None:
             P.gnc_mu_step = float(gnc_mu_step)
         P.use_gpu, P.rtol, P.max_iters = int(bool(gpu)), float(rtol), int(max_iters)
+        if max_translation_error is not None:
+            P.max_translation_error = float(max_translation_error)
+        if clique_node_budget is not None:
+            P.clique_node_budget = int(clique_node_budget)
         T = np.empty(self.n * d * (d + 1))
         F = np.empty(K * d * (d + 1))
         par = np.empty(K, np.int32); cand = np.empty(K, np.int32); inl = np.empty(K, np.int32)
@@ -1379,6 +1405,33 @@ class Graph:
         frames = np.ascontiguousarray(F.reshape(K, d + 1, d).transpose(0, 2, 1))
         return from_dev_layout(T, d), frames, dict(parent=par, candidates=cand, inliers=inl,
                                                    edge_inlier=ei[:self.m], iters=it.value, relres=rr.value)
+
+    def pcm(self, agent_of_pose, T_local, max_translation_error=None, max_rotation_error=None,
+            clique_node_budget=None, gpu=False):
+        """Pairwise consistent set of the inter-agent loop closures (dpgo_graph_pcm): every agent pair's shared
+        closures are one group of pair_consistency (candidate = the pair's relative frame each closure implies under
+        T_local, d x (d+1) n as distributed_init_ex returns it), the group's maximum clique its inliers.  Returns
+        (edge_inlier [m] uint8: 1 inlier / 0 rejected / 255 an edge inside one agent, info dict(groups, candidates,
+        pair_tests, inliers, min_clique_ratio, unproven)).  max_translation_error has no default."""
+        aop, ap = _i32(agent_of_pose)
+        P = InitParams()
+        lib().dpgo_default_init_params(C.byref(P))
+        if max_rotation_error is not None:
+            P.max_rotation_error = float(max_rotation_error)
+        if max_translation_error is not None:
+            P.max_translation_error = float(max_translation_error)
+        if clique_node_budget is not None:
+            P.clique_node_budget = int(clique_node_budget)
+        P.use_gpu = int(bool(gpu))
+        T = np.asarray(T_local, dtype=np.float64)
+        if T.shape != (self.d, (self.d + 1) * self.n):
+            raise DPGOHipError("pcm: T_local must be d x (d+1) n")
+        Tf, Tp = _f64(to_dev_layout(T))
+        ei = np.empty(max(self.m, 1), np.uint8)
+        info = PcmInfo()
+        _check(lib().dpgo_graph_pcm(self.h, int(aop.max()) + 1, ap, Tp, C.byref(P), ei.ctypes.data_as(_ubp),
+                                    C.byref(info)))
+        return ei[:self.m], {k: getattr(info, k) for k, _ in PcmInfo._fields_}
 
     def chain_init_dev_layout(self, r, YLift):
         Y, Yp = _f64(np.asarray(YLift, dtype=np.float64).T.ravel())
@@ -1558,6 +1611,113 @@ class Graph:
         out = np.empty(self.n, np.int32)
         _check(lib().dpgo_graph_grid_partition(self.h, int(agents_per_axis), out.ctypes.data_as(_ip)))
         return out
+
+
+def _pcm_inputs(F, x, d, group_off):
+    F = np.ascontiguousarray(F, dtype=np.float64).reshape(-1, d * (d + 1))
+    x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, d)
+    if F.shape[0] != x.shape[0]:
+        raise DPGOHipError("pair_consistency: F and x must hold the same number of candidates")
+    go = np.ascontiguousarray(group_off, dtype=np.int32).reshape(-1)
+    if go.size < 1:
+        raise DPGOHipError("pair_consistency: group_off needs ngroups + 1 entries")
+    return F, x, go
+
+
+def pair_consistency_words(group_off, capacity=-1):
+    """Offsets (int64 [ngroups + 1]) of every group's adjacency rows: m_g rows of ceil(m_g / 64) 64-bit words each."""
+    go = np.ascontiguousarray(group_off, dtype=np.int32).reshape(-1)
+    wo = np.zeros(go.size, np.int64)
+    _check(lib().dpgo_hip_pair_consistency_words(go.size - 1, go.ctypes.data_as(_ip), wo.ctypes.data_as(_lp),
+                                                 int(capacity)))
+    return wo
+
+
+def _pair_consistency(fn, F, x, d, group_off, c_R, c_t, dense, capacity):
+    F, x, go = _pcm_inputs(F, x, d, group_off)
+    m, ng = F.shape[0], go.size - 1
+    wo = pair_consistency_words(go)
+    cap = int(wo[-1]) if capacity is None else int(capacity)
+    adj = np.zeros(max(cap, 1), np.uint64)
+    deg = np.zeros(max(m, 1), np.int32)
+    nd = int(np.sum(np.diff(go).astype(np.int64) ** 2)) if dense else 0
+    er = np.empty(max(nd, 1)) if dense else None
+    et = np.empty(max(nd, 1)) if dense else None
+    _check(fn(int(d), m, F.ctypes.data_as(_dp), x.ctypes.data_as(_dp), ng, go.ctypes.data_as(_ip), float(c_R),
+              float(c_t), adj.ctypes.data_as(_ullp), cap, deg.ctypes.data_as(_ip), _opt_ptr(er), _opt_ptr(et)))
+    out = dict(adj=adj[:int(wo[-1])], word_off=wo, degree=deg[:m], group_off=go)
+    if dense:
+        out["e_rot"], out["e_tra"] = er[:nd], et[:nd]
+    return out
+
+
+def pair_consistency(F, x, d, group_off, c_R, c_t, dense=False, capacity=None):
+    """The pair tests of frame candidates on the device (dpgo_hip_pair_consistency): F [m, d (d+1)] column-major
+    frames, x [m, d] lever points, group_off [ngroups + 1].  Returns dict(adj uint64 words, word_off, degree [m],
+    group_off[, e_rot, e_tra: dense m_g x m_g per group, back to back]); adjacency_matrix unpacks a group."""
+    return _pair_consistency(lib().dpgo_hip_pair_consistency, F, x, d, group_off, c_R, c_t, dense, capacity)
+
+
+def pair_consistency_host(F, x, d, group_off, c_R, c_t, dense=False, capacity=None):
+    """pair_consistency by the host twin (dpgo_pair_consistency_host): no device, the same bits."""
+    return _pair_consistency(lib().dpgo_pair_consistency_host, F, x, d, group_off, c_R, c_t, dense, capacity)
+
+
+def pair_consistency_dev(d, m, F_dev: int, x_dev: int, group_off, c_R, c_t, adj_dev: int, adj_capacity, degree_dev: int,
+                         e_rot_dev: int | None = None, e_tra_dev: int | None = None, stream_ptr: int | None = None):
+    """pair_consistency on device pointers (group_off: host), queued on `stream_ptr`; returns once the stream has run
+    it."""
+    go = np.ascontiguousarray(group_off, dtype=np.int32).reshape(-1)
+    _check(lib().dpgo_hip_pair_consistency_dev(int(d), int(m), C.c_void_p(F_dev), C.c_void_p(x_dev), go.size - 1,
+                                               go.ctypes.data_as(_ip), float(c_R), float(c_t), C.c_void_p(adj_dev),
+                                               int(adj_capacity), C.c_void_p(degree_dev), C.c_void_p(e_rot_dev or 0),
+                                               C.c_void_p(e_tra_dev or 0), C.c_void_p(stream_ptr or 0)))
+
+
+def pair_consistency_bench(d, m, F_dev: int, x_dev: int, group_off, c_R, c_t, adj_dev: int, adj_capacity,
+                           degree_dev: int, warmup=5, reps=20):
+    """Milliseconds of `reps` launches of the pair-test kernel (with its degree memset) after `warmup`, each between
+    two HIP events, the tile table uploaded once beforehand (dpgo_hip_pair_consistency_bench)."""
+    go = np.ascontiguousarray(group_off, dtype=np.int32).reshape(-1)
+    ms = np.empty(int(reps))
+    _check(lib().dpgo_hip_pair_consistency_bench(int(d), int(m), C.c_void_p(F_dev), C.c_void_p(x_dev), go.size - 1,
+                                                 go.ctypes.data_as(_ip), float(c_R), float(c_t), C.c_void_p(adj_dev),
+                                                 int(adj_capacity), C.c_void_p(degree_dev), int(warmup), int(reps),
+                                                 ms.ctypes.data_as(_dp)))
+    return ms
+
+
+def adjacency_matrix(adj, word_off, group_off, g):
+    """Group g of a pair_consistency result as a bool matrix [m_g, m_g] (entry (k, l) = bit l of row k)."""
+    mg = int(group_off[g + 1] - group_off[g])
+    W = (mg + 63) // 64
+    rows = np.asarray(adj[int(word_off[g]):int(word_off[g]) + mg * W], dtype=np.uint64).reshape(mg, W)
+    bits = np.unpackbits(rows.view(np.uint8).reshape(mg, W * 8), axis=1, bitorder="little")
+    return bits[:, :mg].astype(bool)
+
+
+def pack_adjacency(A):
+    """A bool matrix [m, m] as max_clique's rows: uint64 [m, ceil(m / 64)], bit l of row k = A[k, l]."""
+    A = np.asarray(A, dtype=bool)
+    m = A.shape[0]
+    W = max((m + 63) // 64, 1)
+    bits = np.zeros((m, W * 64), np.uint8)
+    bits[:, :m] = A
+    return np.packbits(bits, axis=1, bitorder="little").view(np.uint64).reshape(m, W)
+
+
+def max_clique(rows, m=None, node_budget=-1):
+    """Maximum clique of the graph whose row k is rows[k] (uint64 words, as pack_adjacency / a group's adj reshaped
+    [m_g, words]): (members ascending, proven).  node_budget < 0: no limit; 0: the greedy clique (descending degree,
+    ties to the lower index), proven False unless m = 0."""
+    rows = np.ascontiguousarray(rows, dtype=np.uint64)
+    m = rows.shape[0] if m is None else int(m)
+    W = rows.shape[1] if rows.ndim == 2 else (m + 63) // 64
+    cl = np.empty(max(m, 1), np.int32)
+    size, proven = C.c_int(), C.c_int()
+    _check(lib().dpgo_max_clique(m, int(W), rows.ctypes.data_as(_ullp), int(node_budget), cl.ctypes.data_as(_ip),
+                                 C.byref(size), C.byref(proven)))
+    return cl[:size.value].copy(), bool(proven.value)
 
 
 def robust_rotation_average(R, kappa=None, threshold=None, max_iters=1000, mu_step=1.4):

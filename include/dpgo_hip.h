@@ -524,6 +524,60 @@ int dpgo_hip_relative_poses(int d, int n, const double* T, int m, const int* p1,
 int dpgo_hip_relative_poses_dev(int d, long long n, const double* T_dev, long long m, const int* p1_dev,
                                 const int* p2_dev, double* R_out_dev, double* t_out_dev, void* stream);
 
+/* ---- pairwise consistency of frame candidates (build-defined) ----------------------
+ * A candidate k is a rigid frame F_k = [R_k | t_k] (d x (d+1) column-major, d (d+1) doubles) plus a lever point
+ * x_k (d doubles); a group is a contiguous run of candidates that should all describe one frame (group g holds
+ * candidates group_off[g] .. group_off[g+1]; sizes 0 and 1 are allowed; group_off[0] = 0, ascending,
+ * group_off[ngroups] = m).  For two candidates of one group, with dR = R_k - R_l and dt = t_k - t_l formed first:
+ *   e_rot(k,l) = |dR|_F^2,   e_tra(k,l) = 1/2 (|dR x_k + dt|^2 + |dR x_l + dt|^2),
+ *   A(k,l) = 1 iff k != l and e_rot <= c_R^2 and e_tra <= c_t^2   (any NaN gives 0; the diagonal is 0).
+ * (l,k) is the exact negation of (k,l), so A and both e are bitwise symmetric.  One operation order per d, shared
+ * by the kernel and the host twin, multiplications and additions never contracted: per entry of dR in storage
+ * order, df = R_k - R_l, e_rot = e_rot + df df; per lever x and row i, v = dR[i,0] x[0], v = v + dR[i,c] x[c]
+ * (c = 1 .. d-1), v = v + dt[i], s = s + v v; e_tra = 0.5 (s_k + s_l); c_R^2 = c_R c_R and c_t^2 = c_t c_t.
+ * Outputs: adj -- per group g of size m_g, m_g rows of ceil(m_g / 64) 64-bit words at word_off[g]
+ * (dpgo_hip_pair_consistency_words), bit l % 64 of word l / 64 of row k = A(k,l), padding bits zero, groups back to
+ * back; degree[m] -- the row popcounts; e_rot / e_tra (each may be NULL; tests and diagnostics) -- dense m_g x m_g
+ * doubles per group, entry (k,l) at k m_g + l, groups back to back at sum of the earlier m_g^2, refused when the sum
+ * of m_g^2 passes DPGO_PCM_DENSE_MAX.  adj_capacity: the words the caller's adj holds (< 0: not checked).  m = 0 or ngroups = 0 writes
+ * nothing.  DPGO_HIP_EINVAL for d outside {2, 3}, m < 0, ngroups < 0, a null required pointer, a group_off that
+ * does not start at 0, descends or does not end at m, or a capacity below the words needed. */
+#define DPGO_PCM_DENSE_MAX (1LL << 26)
+/* word_off[ngroups + 1]: the offset of every group's rows in adj (word_off[ngroups] = the total).  capacity < 0:
+ * no limit; else DPGO_HIP_EINVAL when the total passes it, as when it does not fit a long long. */
+int dpgo_hip_pair_consistency_words(int ngroups, const int* group_off, long long* word_off, long long capacity);
+/* Host pointers in and out; one kernel launch over a host-built table of (group, row tile, column tile) 64 x 64
+ * tiles, one integer-atomic degree count.  Synchronises. */
+int dpgo_hip_pair_consistency(int d, int m, const double* F, const double* x, int ngroups, const int* group_off,
+                              double c_R, double c_t, unsigned long long* adj, long long adj_capacity, int* degree,
+                              double* e_rot, double* e_tra);
+/* The same on device pointers (group_off stays a host array: the tile table is built from it), queued on `stream`;
+ * the call returns after the stream has run it (its tile table is released then). */
+int dpgo_hip_pair_consistency_dev(int d, int m, const double* F_dev, const double* x_dev, int ngroups,
+                                  const int* group_off, double c_R, double c_t, unsigned long long* adj_dev,
+                                  long long adj_capacity, int* degree_dev, double* e_rot_dev, double* e_tra_dev,
+                                  void* stream);
+/* Measurement: the tile table is built and uploaded once, then warmup + reps launches (degree memset + kernel, no
+ * dense outputs) run on the null stream, each between two HIP events; ms[reps] receives the timed launches'
+ * milliseconds.  m >= 1. */
+int dpgo_hip_pair_consistency_bench(int d, int m, const double* F_dev, const double* x_dev, int ngroups,
+                                    const int* group_off, double c_R, double c_t, unsigned long long* adj_dev,
+                                    long long adj_capacity, int* degree_dev, int warmup, int reps, double* ms);
+/* The host twin: no device, the same bits (adj, degree, e_rot, e_tra). */
+int dpgo_pair_consistency_host(int d, int m, const double* F, const double* x, int ngroups, const int* group_off,
+                               double c_R, double c_t, unsigned long long* adj, long long adj_capacity, int* degree,
+                               double* e_rot, double* e_tra);
+/* Maximum clique of the graph on m vertices whose row k is adj_rows[k words_per_row ..] (bit l of the row = an
+ * edge k-l; symmetric, zero diagonal and zero padding, as dpgo_hip_pair_consistency leaves a group: not checked).
+ * Host only, deterministic, one thread: a bitset branch and bound (Tomita's colour bound, popcounts).  The first
+ * incumbent is the greedy clique that walks the vertices by descending degree, ties to the lower index, and keeps
+ * every vertex adjacent to all kept so far.  node_budget: the search nodes that may be expanded (< 0: no limit; 0:
+ * the greedy clique alone).  proven = 1: the search finished and clique[0 .. size) is a maximum clique; proven = 0:
+ * the best clique found within the budget.  Members ascending.  m = 0: size 0, proven 1.  DPGO_HIP_EINVAL for
+ * m < 0, words_per_row < ceil(m / 64) or a null pointer (adj_rows may be NULL when m = 0). */
+int dpgo_max_clique(int m, int words_per_row, const unsigned long long* adj_rows, long long node_budget, int* clique,
+                    int* size, int* proven);
+
 /* ---- measurement helpers ----------------------------------------------------------------*/
 /* Select a compiled kernel variant / host sequence for A/B timing (process-wide; every setting gives
  * results within the documented bars, most bitwise the default's).  key 0: BSR X.Q SpMM

@@ -93,6 +93,7 @@ int dpgo_robust_rotation_average(int d, int n, const double* R, const double* ka
 #define DPGO_LOCAL_ODOMETRY 1 /* odometryInitialization: what localInitialization does under any robust cost */
 #define DPGO_ALIGN_L2 0               /* dpgo_graph_distributed_init's average over every shared closure */
 #define DPGO_ALIGN_ROBUST_TWO_STAGE 1 /* computeRobustNeighborTransformTwoStage (src/PGOAgent.cpp:290-331) */
+#define DPGO_ALIGN_PCM 2              /* the maximum set of pairwise consistent candidates (build-defined, below) */
 typedef struct {
   int local_init;            /* DPGO_LOCAL_* (default CHORDAL) */
   int align;                 /* DPGO_ALIGN_* (default L2) */
@@ -102,6 +103,9 @@ typedef struct {
   int use_gpu;               /* chordal solves by Jacobi-PCG on the device (default 0: host Cholesky) */
   double rtol;               /* 1e-12 (use_gpu) */
   int max_iters;             /* 20000 (use_gpu) */
+  /* pairwise consistency (DPGO_ALIGN_PCM, dpgo_graph_pcm); c_R is max_rotation_error */
+  double max_translation_error; /* c_t; 0 = unset: PCM then refuses (the reference has no value for it) */
+  long long clique_node_budget; /* dpgo_max_clique's node_budget per group (default 10,000,000; < 0: no limit) */
 } dpgo_init_params;
 void dpgo_default_init_params(dpgo_init_params* p);
 /* LOCAL_ODOMETRY: each agent composes its odometry edges (both poses in the agent at consecutive local indices,
@@ -114,6 +118,16 @@ void dpgo_default_init_params(dpgo_init_params* p);
  * W_parent-pose T_e (T_e^-1 for an edge leaving A); the rotation is dpgo_robust_rotation_average of the candidates
  * (unit kappa, max_rotation_error), the translation the plain mean of the inlier candidates' translations.  An empty
  * inlier set skips the pair and A waits for another aligned neighbour; DPGO_HIP_EINVAL if an agent is never aligned.
+ * ALIGN_PCM (build-defined, absent from the reference): the breadth-first order, the single parent and the candidate
+ * frames of ALIGN_ROBUST_TWO_STAGE; the candidates of a (parent, child) pair are one group of
+ * dpgo_hip_pair_consistency (include/dpgo_hip.h) with the child's closure pose in its local frame as the lever point,
+ * c_R = max_rotation_error and c_t = max_translation_error (DPGO_HIP_EINVAL naming the field while that is unset);
+ * the inlier set is dpgo_max_clique of the group (clique_node_budget); the rotation is the chordal L2 mean of the
+ * clique's rotations projected to SO(d) (ALIGN_L2's mean with unit weights, on that subset, in candidate order), the
+ * translation the plain mean of the clique's translations.  A single candidate is a clique of one: the agent is
+ * aligned on that closure alone, and so is an agent whose candidates are all mutually inconsistent (on the lowest
+ * index among the highest degrees: the greedy incumbent).  use_gpu = 1 runs the pair tests by the kernel, 0 by the
+ * host twin: the same bits either way.
  * ALIGN_L2 with LOCAL_CHORDAL: frame o local is dpgo_graph_distributed_init's trajectory, bitwise.
  * Outputs: T_local d x (d+1) n column-major (each agent in its own frame); frames num_agents x d x (d+1) column-major
  * (identity for the root); parent[num_agents] (-1 for the root); candidates / inliers [num_agents] (0 for the root);
@@ -123,6 +137,26 @@ int dpgo_graph_distributed_init_ex(dpgo_graph g, int num_agents, const int* agen
                                    const dpgo_init_params* params, double* T_local, double* frames, int* parent,
                                    int* candidates, int* inliers, unsigned char* edge_inlier, int* iters,
                                    double* relres);
+/* Pairwise consistent measurement set (PCM) over the inter-agent loop closures of the whole graph (build-defined,
+ * DESIGN 3.17 and 7 item 17).  Every unordered agent pair A < B with shared closures is one group of
+ * dpgo_hip_pair_consistency; closure k between pose a_k of A and pose b_k of B gives the candidate
+ * F_k = T_local(a_k) Z_k T_local(b_k)^-1 (Z_k^-1 when the edge leaves B): B's local frame in A's, with the lever point
+ * x_k = the translation of T_local(b_k).  T_local: d x (d+1) n column-major, each agent in its own frame
+ * (dpgo_graph_distributed_init_ex's output).  params (NULL = defaults, which refuse: max_translation_error is unset):
+ * max_rotation_error = c_R, max_translation_error = c_t, clique_node_budget, use_gpu (1: the kernel, one launch over
+ * all groups; 0: the host twin; the same bits).  edge_inlier[m]: 1 a member of its group's maximum clique
+ * (dpgo_max_clique), 0 a rejected shared closure, 255 an edge inside one agent.  A group of one closure is trivially
+ * consistent: its closure gets 1.  info (may be NULL): see below. */
+typedef struct {
+  int groups;               /* agent pairs with shared closures */
+  long long candidates;     /* shared closures */
+  long long pair_tests;     /* sum over groups of m_g^2 */
+  long long inliers;        /* entries of edge_inlier equal to 1 */
+  double min_clique_ratio;  /* the smallest clique size / group size (1 without groups) */
+  int unproven;             /* groups whose clique search ended on the node budget */
+} dpgo_pcm_info;
+int dpgo_graph_pcm(dpgo_graph g, int num_agents, const int* agent_of_pose, const double* T_local,
+                   const dpgo_init_params* params, unsigned char* edge_inlier, dpgo_pcm_info* info);
 /* Grid graphs: agent = sub-cube (x/s, y/s, z/s), s = k / A; id = ax + A (ay + A az). */
 /* Certified optimality gap of an iterate X (r x (d+1) n, column-major, e.g. the engine's
  * dpgo_rbcd_get_X gathered over ranks) for the whole graph's central Q (unit weights): lambda_min of
