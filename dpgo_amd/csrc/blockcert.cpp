@@ -12,6 +12,8 @@
 #include <cstring>
 #include <vector>
 
+#include "cert_host.h"
+#include "host_eig.h"
 #include "problem_internal.h"
 
 namespace dpgo {
@@ -19,24 +21,13 @@ namespace {
 
 constexpr double kDropGram = 1e-14;  // directions at or below this share of the largest Gram eigenvalue are dropped
 constexpr double kDropP = 1e-10;     // lambda_min(B) < kDropP lambda_max(B): the iteration runs without P
-constexpr double kSeedKeep = 1e-6;   // eigenvalues of X X^T kept for U, relative to the largest
-constexpr double kSeedDrop = 1e-10;  // a seed whose remainder is below this share of its norm is dropped
 
 // ascending eigenvalues w and eigenvectors (vector c at Z[c * m ..]) of the symmetric part of A (m x m row-major)
 void eig_sym(int m, const std::vector<double>& A, std::vector<double>& Z, std::vector<double>& w) {
   std::vector<double> As(static_cast<size_t>(m) * m);
   for (int i = 0; i < m; ++i)
     for (int j = 0; j < m; ++j) As[static_cast<size_t>(i) * m + j] = 0.5 * (A[static_cast<size_t>(i) * m + j] + A[static_cast<size_t>(j) * m + i]);
-  if (m == 1) {
-    Z.assign(1, 1.0);
-    w.assign(1, As[0]);
-    return;
-  }
-  std::vector<double> Zw;
-  sym_eig(m, As, Zw);
-  w.assign(Zw.begin() + static_cast<long>(m) * m, Zw.end());
-  Zw.resize(static_cast<size_t>(m) * m);
-  Z.swap(Zw);
+  sym_eig(m, As, w, Z);
 }
 
 // T (m x mk row-major) with T^T G T = I on the directions of the Gram matrix G above kDropGram of the largest
@@ -100,51 +91,6 @@ void ritz(int m, const std::vector<double>& A, const std::vector<double>& B, Rit
     }
 }
 
-// The locked block of DPGO_CERT_SEED_X on the host, as dpgo_hip_certify_ex builds it: the principal row directions of
-// X (eigenvalues of X X^T >= kSeedKeep of the largest) and the translation gauge, classical Gram-Schmidt twice, a
-// vector whose remainder is <= kSeedDrop of its norm dropped.  U: nc x (r + 1), zero-padded (the device layout).
-int seed_block(int r, int b, long nc, const double* X, std::vector<double>& U) {
-  const int ru = r + 1;
-  U.assign(static_cast<size_t>(nc) * ru, 0.0);
-  std::vector<double> G(static_cast<size_t>(r) * r, 0.0), Z, w;
-  for (long x = 0; x < nc; ++x)
-    for (int i = 0; i < r; ++i)
-      for (int j = 0; j < r; ++j) G[static_cast<size_t>(i) * r + j] += X[x * r + i] * X[x * r + j];
-  eig_sym(r, G, Z, w);
-  std::vector<int> dirs;
-  for (int e = r - 1; e >= 0; --e)
-    if (w[e] >= kSeedKeep * w[r - 1]) dirs.push_back(e);
-  int nl = 0;
-  std::vector<double> v(nc), c(ru);
-  for (size_t q = 0; q <= dirs.size(); ++q) {
-    for (long x = 0; x < nc; ++x) {
-      double acc = 0.0;
-      if (q < dirs.size())
-        for (int i = 0; i < r; ++i) acc += Z[static_cast<size_t>(dirs[q]) * r + i] * X[x * r + i];
-      else
-        acc = x % b == b - 1 ? 1.0 : 0.0;
-      v[x] = acc;
-    }
-    double n0 = 0.0;
-    for (long x = 0; x < nc; ++x) n0 += v[x] * v[x];
-    n0 = std::sqrt(n0);
-    for (int pass = 0; pass < 2 && nl > 0; ++pass) {
-      std::fill(c.begin(), c.end(), 0.0);
-      for (long x = 0; x < nc; ++x)
-        for (int j = 0; j < nl; ++j) c[j] += v[x] * U[x * ru + j];
-      for (long x = 0; x < nc; ++x)
-        for (int j = 0; j < nl; ++j) v[x] -= c[j] * U[x * ru + j];
-    }
-    double n1 = 0.0;
-    for (long x = 0; x < nc; ++x) n1 += v[x] * v[x];
-    n1 = std::sqrt(n1);
-    if (!(n1 > kSeedDrop * n0)) continue;  // in the span of the previous ones
-    for (long x = 0; x < nc; ++x) U[x * ru + nl] = v[x] / n1;
-    ++nl;
-  }
-  return nl;
-}
-
 }  // namespace
 }  // namespace dpgo
 
@@ -175,7 +121,7 @@ int dpgo_hip_certify_block(dpgo_hip_problem h, const double* X, const dpgo_block
   const long nc = static_cast<long>(h->N) * b, L = nc * r;
   // the locked block U first (host only), so the size refusal comes before any device work
   std::vector<double> Uh;
-  const int nl = (P.flags & DPGO_CERT_SEED_X) ? seed_block(r, b, nc, X, Uh) : 0;
+  const int nl = (P.flags & DPGO_CERT_SEED_X) ? seed_block(r, b, nc, X, SeedLayout::Interleaved, Uh) : 0;
   if (3L * r > nc - nl)
     return fail(DPGO_HIP_EINVAL, "block certification: three blocks of r rows exceed the free dimension (d+1) n - seeds");
   DPGO_TRY(problem_ready(h));
@@ -199,17 +145,8 @@ int dpgo_hip_certify_block(dpgo_hip_problem h, const double* X, const dpgo_block
   // Lambda(X) into h->S (the S the Riemannian Hessian uses); X itself travels through the W block
   HIP_TRY(hipMemcpyAsync(W, X, sizeof(double) * L, hipMemcpyHostToDevice, st));
   DPGO_TRY(eval_at(h, W, h->tA.p, h->S.p, h->pa.p, FLAG_NONE));
-  {  // the start block: the Lanczos certificate's SplitMix64 stream in the lifted layout's memory order
-    std::vector<double> q0(L);
-    unsigned long long s = 0x5EEDULL;
-    for (long x = 0; x < L; ++x) {
-      s += 0x9E3779B97F4A7C15ULL;
-      unsigned long long z = s;
-      z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-      z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-      z ^= z >> 31;
-      q0[x] = 2.0 * (static_cast<double>(z >> 11) * (1.0 / 9007199254740992.0)) - 1.0;
-    }
+  {  // the start block: the Lanczos certificate's stream in the lifted layout's memory order
+    const std::vector<double> q0 = cert_start(CertStart::Lifted, L, r);
     HIP_TRY(hipMemcpyAsync(Xb, q0.data(), sizeof(double) * L, hipMemcpyHostToDevice, st));
     HIP_TRY(hipStreamSynchronize(st));  // q0 and Uh are read
   }
@@ -463,19 +400,7 @@ int dpgo_hip_certify_block(dpgo_hip_problem h, const double* X, const dpgo_block
   HIP_TRY(hipStreamSynchronize(st));
   // outputs, only now that nothing can fail
   *lambda_min = lam;
-  if (info) {
-    info->iters = passes;
-    info->restarts = restarts;
-    info->seeds = nl;
-    info->residual = res;
-    info->lambda_seed = lam_s;
-    info->lambda_complement = theta_c;
-    info->residual_complement = res_c;
-    info->coupling = coupling;
-    const double cl = theta_c - res_c;
-    info->lower_bound = nl > 0 ? 0.5 * (lam_s + cl) - std::sqrt(0.25 * (cl - lam_s) * (cl - lam_s) + coupling * coupling) : cl;
-    for (int i = 0; i < 8; ++i) info->ritz[i] = i < r ? theta[i] : NAN;
-  }
+  if (info) fill_cert_info(info, passes, restarts, nl, res, lam_s, theta_c, res_c, coupling, theta);
   if (eigvec)  // the unit vector on row 0, rows 1.. zero, as dpgo_hip_escape_direction takes it
     for (long x = 0; x < nc; ++x) {
       eigvec[x * r] = ev[x * r];

@@ -20,6 +20,7 @@
 #include <thread>
 #include <type_traits>
 
+#include "cert_host.h"
 #include "problem_internal.h"
 
 namespace dpgo {
@@ -608,27 +609,8 @@ int dpgo_hip_certify_chol_ex(dpgo_hip_problem h, const double* X, double eta, co
   HIP_TRY(coef.ensure(1));
   double* v = vy.p;
   double* y = vy.p + L;
-  auto dots = [&](const double* x, const double* B, int k, double* out) -> int {
-    HIP_TRY(launch_dot_multi(L, x, B, k, part.p, h->stream));
-    std::vector<double> hp(static_cast<size_t>(kDotBlocks) * k);
-    HIP_TRY(hipMemcpyAsync(hp.data(), part.p, sizeof(double) * hp.size(), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    for (int j = 0; j < k; ++j) out[j] = 0.0;
-    for (int g = 0; g < kDotBlocks; ++g)
-      for (int j = 0; j < k; ++j) out[j] += hp[static_cast<size_t>(g) * k + j];
-    return DPGO_HIP_OK;
-  };
-  {  // seeded start (SplitMix64 uniform in [-1, 1), the Lanczos certificate's stream) on row 0
-    std::vector<double> q0(L, 0.0);
-    unsigned long long st = 0x5EEDULL;
-    for (long x = 0; x < L; x += r) {
-      st += 0x9E3779B97F4A7C15ULL;
-      unsigned long long z = st;
-      z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-      z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-      z ^= z >> 31;
-      q0[x] = 2.0 * (static_cast<double>(z >> 11) * (1.0 / 9007199254740992.0)) - 1.0;
-    }
+  {  // seeded start on row 0
+    const std::vector<double> q0 = cert_start(CertStart::Row0Dense, L, r);
     HIP_TRY(hipMemcpyAsync(v, q0.data(), sizeof(double) * L, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
   }
@@ -642,20 +624,20 @@ int dpgo_hip_certify_chol_ex(dpgo_hip_problem h, const double* X, double eta, co
     DPGO_TRY(sweep_backward(h, view));
     ++it;
     double nn = 0.0;
-    DPGO_TRY(dots(h->tB.p, h->tB.p, 1, &nn));
+    DPGO_TRY(dot_multi_host(L, h->tB.p, h->tB.p, 1, part.p, h->stream, &nn));
     if (!(nn > 0.0) || !std::isfinite(nn))
       return fail(DPGO_HIP_EDEVICE, "certification: the inverse iteration broke down");
     HIP_TRY(launch_scale(L, h->tB.p, 1.0 / std::sqrt(nn), v, h->stream));
     const SpmmArgs sa{v, nullptr, nullptr, nullptr, h->S.p, y, nullptr, nullptr, nullptr, PRECON_NONE};
     DPGO_TRY(spmm_launch(h, MODE_CERT, make_ctx(h, FLAG_NONE, nullptr), sa));
     double d2[2];
-    DPGO_TRY(dots(y, vy.p, 2, d2));  // <y, v>, <y, y>
+    DPGO_TRY(dot_multi_host(L, y, vy.p, 2, part.p, h->stream, d2));  // <y, v>, <y, y>
     lam = d2[0];
     // the residual y - lam v itself (|y|^2 - lam^2 cancels where the pair has converged)
     HIP_TRY(hipMemcpyAsync(coef.p, &lam, sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(launch_axpy_multi(L, y, v, 1, coef.p, h->stream));
     double rr = 0.0;
-    DPGO_TRY(dots(y, y, 1, &rr));
+    DPGO_TRY(dot_multi_host(L, y, y, 1, part.p, h->stream, &rr));
     res = std::sqrt(std::max(rr, 0.0));
     if (res <= P.tol * sigma_top) break;
   }

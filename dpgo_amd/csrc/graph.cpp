@@ -16,25 +16,18 @@
 #include <utility>
 #include <vector>
 
+#include "cert_host.h"
 #include "graph_internal.h"
 
 using namespace dpgo;
 
 namespace {
 
-struct SplitMix64 {
-  uint64_t state;
+// the shared stream with the oracle's Box-Muller normal() on top (both values of a pair are used)
+struct NormalStream : SplitMix64 {
   bool has = false;
   double cached = 0.0;
-  explicit SplitMix64(uint64_t s) : state(s) {}
-  uint64_t next() {
-    state += 0x9E3779B97F4A7C15ULL;
-    uint64_t z = state;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    return z ^ (z >> 31);
-  }
-  double uniform() { return static_cast<double>(next() >> 11) * (1.0 / 9007199254740992.0); }
+  using SplitMix64::SplitMix64;
   double normal() {
     if (has) {
       has = false;
@@ -316,7 +309,7 @@ int dpgo_graph_grid3d(int k, unsigned long long seed, double rot_sigma, double t
     std::sort(hi.begin(), hi.end());
     for (int j : hi) edges.emplace_back(i, j);
   }
-  SplitMix64 rng(seed);
+  NormalStream rng(seed);
   std::vector<double> Rgt(static_cast<size_t>(n) * 9);
   for (int i = 0; i < n; ++i) {
     double q[4];
@@ -368,7 +361,7 @@ int dpgo_graph_grid3d(int k, unsigned long long seed, double rot_sigma, double t
 int dpgo_graph_grid3d_truth(int k, unsigned long long seed, double* T_out) {
   if (!T_out || k < 2 || k > 200) return fail(DPGO_HIP_EINVAL, "grid side must be in [2, 200] and T_out non-null");
   const int n = k * k * k, kk = k * k;
-  SplitMix64 rng(seed);
+  NormalStream rng(seed);
   for (int i = 0; i < n; ++i) {
     double q[4];
     for (double& x : q) x = rng.normal();

@@ -377,9 +377,12 @@ struct ScopedEvents {
 // launches of a standalone kernel benchmark that run before its timed window
 constexpr int kBenchWarmup = 3;
 
-// Eigenpairs of the dense symmetric m x m matrix A (row-major), capi.cpp: Z = the eigenvectors (vector c at
-// Z[c * m ..]) followed by the m ascending eigenvalues
-void sym_eig(int m, std::vector<double> A, std::vector<double>& Z);
+// certify.cpp: out[j] = <x, B_j>, j < k, over vectors of L doubles (B_j at B + j L) by launch_dot_multi into `part`
+// (kDotBlocks k doubles on the device), its partials summed on the host in a fixed order (synchronises)
+int dot_multi_host(long L, const double* x, const double* B, int k, double* part, hipStream_t stream, double* out);
+// certify.cpp: the fields of dpgo_cert_info and its lower bound from a certificate's quantities (ritz: theta's first 8)
+void fill_cert_info(dpgo_cert_info* info, int iters, int restarts, int nl, double res, double lam_s, double theta_c,
+                    double res_c, double coupling, const std::vector<double>& theta);
 
 // exact.cpp: the exact preconditioner.  sync_chol brings the factor up to date with Q (symbolic build + upload on a
 // new pattern, the numeric factorisation alone after a reweighting); exact_precond applies it:

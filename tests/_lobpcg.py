@@ -1,6 +1,7 @@
 """The block certificate (dpgo_hip_certify_block) restated in numpy on a dense S (test infrastructure,
-no GPU): the same start stream, the same locked block U, the same drop and refresh rules and the same lower bound as
-dpgo_amd/csrc/blockcert.cpp, with numpy's eigh where the library runs its host Jacobi/Householder solver.  Vectors
+no GPU): the same start stream and the same locked block U as dpgo_amd/csrc/cert_host.cpp (cert_start, seed_block),
+the same drop and refresh rules and the same lower bound as dpgo_amd/csrc/blockcert.cpp, with numpy's eigh where the
+library runs its host Householder/QL solver (dpgo_amd/csrc/host_eig.cpp).  Vectors
 are rows (V -> V S), as the lifted r x (d+1) n layout holds them.  The result's `iters` counts operator applications
 the way the library's info.iters does; `iterations` counts the loop's turns.
 

@@ -196,6 +196,20 @@ def test_cpp_tcg_plan():
         assert f"[PASS] {name}" in out, out[-3000:]
 
 
+def test_cpp_cert_host():
+    """The certificates' host numerics (dpgo_amd/csrc/host_eig.cpp, cert_host.cpp): the dense and tridiagonal
+    eigen-solvers against residual and orthogonality bounds on random, degenerate, graded and restart-shaped matrices,
+    the start stream's three placement rules, the locked seed block on full-rank and rank-deficient X, and the
+    Lanczos plan's hand-worked rows."""
+    binary = os.path.join(ROOT, "dpgo_amd", "cpp", "build", "test_cert_host")
+    assert os.path.exists(binary), "C++ tests not built (run __graft_entry__.build())"
+    p = subprocess.run([binary], capture_output=True, text=True, timeout=60)
+    out = p.stdout + p.stderr
+    assert p.returncode == 0, out[-3000:]
+    for name in ["SymEig", "TridiagValues", "TridiagLowestVector", "StartStream", "SeedBlock", "LanczosPlan"]:
+        assert f"[PASS] {name}" in out, out[-3000:]
+
+
 @pytest.mark.parametrize("name,agents", [("smallGrid3D", 5), ("input_INTEL_g2o", 4), ("city10000", 8)])
 def test_distributed_initialization_matches_oracle(H, name, agents):
     """PGOAgent::localInitialization per agent + initializeInGlobalFrame (host Cholesky path) vs the
