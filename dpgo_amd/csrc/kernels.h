@@ -532,8 +532,10 @@ hipError_t launch_pair_consistency(int d, long ntiles, const PcmTile* tiles, con
                                    double* e_rot, double* e_tra, hipStream_t stream);
 // PGOAgent::computeConvergedLoopClosureRatio (src/PGOAgent.cpp:1247-1289): per agent a, the share of
 // its loop closures idx[off[a] .. off[a+1]) whose weight w[] is exactly 1 or 0 (0/0 = NaN, as there)
+// fixed (may be null): one flag per entry of w[]; a flagged copy (a known inlier, :1257 / :1266) is left out of both
+// the converged count and the total.  Null runs the kernel without the flag loads, as before the flags existed.
 hipError_t launch_conv_ratio(int num_agents, const int* off, const int* idx, const double* w, double* ratio,
-                             hipStream_t stream);
+                             const unsigned char* fixed, hipStream_t stream);
 // partial |A - B|^2 per tile (no output vector)
 hipError_t launch_sqdiff(int r, int b, const LaunchCtx& c, const double* A, const double* Bv);
 hipError_t launch_select(int r, int b, const LaunchCtx& c, const double* A, const double* Bv, const int* use_a,
@@ -572,8 +574,24 @@ hipError_t launch_edge_reweight(int d, int m, int n, const double* raw, const in
                                 hipStream_t stream);
 hipError_t launch_gnc_snapshot(int r, int b, const GncEntries& g, const double* X, const double* RX, const int* mask,
                                hipStream_t stream);
+// fixed (may be null): one flag per entry of g; a flagged entry returns before anything is written, like one whose
+// neighbour pose has not arrived.  Null runs the instantiation without the flag load.
 hipError_t launch_gnc_weights(int r, int b, const GncEntries& g, const double* X, const double* RX,
-                              const RobustParams& rp, double* w_prob, double* w_g, hipStream_t stream);
+                              const RobustParams& rp, double* w_prob, double* w_g, const unsigned char* fixed,
+                              hipStream_t stream);
+// dpgo_rbcd_set_weights for one colour: gathers the caller's per-graph-edge weights w (and flags `fixed`, may be null)
+// into the colour's destinations, one thread per destination -- w_prob[n_prob], w_g[n_g], then with flags
+// fix_gnc[n_gnc] and fix_prob[n_prob].  src[n_prob + n_g + n_gnc]: the graph edge of every destination of the first
+// three ranges in destination order (the fourth range reuses the first's).  Contiguous stores, gathered loads.
+struct SetWeights {
+  int n_prob, n_g, n_gnc;
+  const int* src;
+  double* w_prob;
+  double* w_g;
+  unsigned char* fix_gnc;
+  unsigned char* fix_prob;
+};
+hipError_t launch_set_weights(const SetWeights& s, const double* w, const unsigned char* fixed, hipStream_t stream);
 // Lanczos helpers over flat vectors of length len: partial[g * k + j] = sum over grid block g's
 // chunk of w . basis_j (fixed grid kDotBlocks, fixed order); w -= sum_j c_j basis_j (c on device)
 constexpr int kDotBlocks = 512;

@@ -4163,13 +4163,19 @@ __device__ __forceinline__ double robust_weight(const RobustParams& p, double r)
 
 // One thread per loop closure: computeMeasurementError (src/DPGO_utils.cpp:509-515)
 //   kappa |Y1 R - Y2|^2 + tau |p2 - p1 - Y1 t|^2, residual = sqrt, weight.
-template <int R, int D>
+// FIXED: fixed[e] != 0 marks a known inlier (isKnownInlier, :1186 / :1203): its weight stays what was set.  The
+// FIXED = false instantiation never reads the argument and is the kernel as it was before the flags existed.
+template <int R, int D, bool FIXED>
 __global__ __launch_bounds__(kThreads) void k_gnc_weights(GncEntries g, const double* __restrict__ X,
                                                           const double* __restrict__ RX, RobustParams rp,
-                                                          double* __restrict__ w_prob, double* __restrict__ w_g) {
+                                                          double* __restrict__ w_prob, double* __restrict__ w_g,
+                                                          const unsigned char* __restrict__ fixed) {
   constexpr int B = D + 1;
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= g.n) return;
+  if constexpr (FIXED) {
+    if (fixed[e] != 0) return;
+  }
   const int s1 = g.src1[e], s2 = g.src2[e], ne = g.nbr_end[e];
   if (ne >= 0 && g.dict_ok[e] == 0) return;  // no neighbour pose received yet: weight unchanged (:1208-1212)
   const double* D_ = ne >= 0 ? g.dict + static_cast<long>(e) * (R * B) : nullptr;
@@ -4217,30 +4223,73 @@ __global__ __launch_bounds__(kThreads) void k_gnc_snapshot(GncEntries g, const d
   if (q == 0) g.dict_ok[e] = 1;
 }
 
-// One block per agent: converged (w == 1 or w == 0) over all loop closures of the agent.
+// One block per agent: converged (w == 1 or w == 0) over all loop closures of the agent.  FIXED: a copy with
+// fixed[idx[i]] != 0 (a known inlier, :1257 / :1266) is left out of the converged count and of the total, which is
+// then counted; the FIXED = false instantiation is the kernel as it was before the flags existed.
+template <bool FIXED>
 __global__ __launch_bounds__(kThreads) void k_conv_ratio(const int* __restrict__ off, const int* __restrict__ idx,
-                                                         const double* __restrict__ w, double* __restrict__ ratio) {
+                                                         const double* __restrict__ w, double* __restrict__ ratio,
+                                                         const unsigned char* __restrict__ fixed) {
   __shared__ int cnt[2];
   const int a = blockIdx.x;
   if (threadIdx.x < 2) cnt[threadIdx.x] = 0;
   __syncthreads();
-  int conv = 0;
+  int conv = 0, counted = 0;
   for (int i = off[a] + threadIdx.x; i < off[a + 1]; i += kThreads) {
+    if constexpr (FIXED) {
+      if (fixed[idx[i]] != 0) continue;
+      counted += 1;
+    }
     const double v = w[idx[i]];
     conv += (v == 1.0 || v == 0.0) ? 1 : 0;
   }
   atomicAdd(&cnt[0], conv);  // integer sums: order-independent
+  if constexpr (FIXED) atomicAdd(&cnt[1], counted);
   __syncthreads();
   if (threadIdx.x == 0) {
-    const double total = static_cast<double>(off[a + 1] - off[a]);
+    const double total = static_cast<double>(FIXED ? cnt[1] : off[a + 1] - off[a]);
     ratio[a] = static_cast<double>(cnt[0]) / total;
   }
 }
 
 hipError_t launch_conv_ratio(int num_agents, const int* off, const int* idx, const double* w, double* ratio,
-                             hipStream_t stream) {
+                             const unsigned char* fixed, hipStream_t stream) {
   if (num_agents == 0) return hipSuccess;
-  k_conv_ratio<<<num_agents, kThreads, 0, stream>>>(off, idx, w, ratio);
+  if (fixed)
+    k_conv_ratio<true><<<num_agents, kThreads, 0, stream>>>(off, idx, w, ratio, fixed);
+  else
+    k_conv_ratio<false><<<num_agents, kThreads, 0, stream>>>(off, idx, w, ratio, nullptr);
+  return hipGetLastError();
+}
+
+// dpgo_rbcd_set_weights: one thread per destination of one colour.  The destinations are, in this order, the colour
+// problem's n_prob edge weights (w_prob), the n_g G entries' weights (w_g), then -- only when flags are given --
+// one flag per GNC entry (fix_gnc, n_gnc) and one per problem edge (fix_prob, n_prob: what k_conv_ratio reads).
+// src holds the graph edge of every destination of the first three ranges, destination-ordered; the fourth reuses
+// the first range's.  Reads gather from the graph-order arrays w / fixed, stores are contiguous.
+__global__ __launch_bounds__(kThreads) void k_set_weights(SetWeights s, const double* __restrict__ w,
+                                                          const unsigned char* __restrict__ fixed) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int n_w = s.n_prob + s.n_g;
+  if (t < s.n_prob) {
+    s.w_prob[t] = w[s.src[t]];
+  } else if (t < n_w) {
+    s.w_g[t - s.n_prob] = w[s.src[t]];
+  } else if (fixed == nullptr) {
+    return;
+  } else if (t < n_w + s.n_gnc) {
+    s.fix_gnc[t - n_w] = fixed[s.src[t]];
+  } else if (t < n_w + s.n_gnc + s.n_prob) {
+    const int u = t - n_w - s.n_gnc;
+    s.fix_prob[u] = fixed[s.src[u]];
+  }
+}
+
+hipError_t launch_set_weights(const SetWeights& s, const double* w, const unsigned char* fixed, hipStream_t stream) {
+  const long total = static_cast<long>(s.n_prob) + s.n_g + (fixed ? static_cast<long>(s.n_gnc) + s.n_prob : 0);
+  if (total == 0) return hipSuccess;
+  const int grid = static_cast<int>((total + kThreads - 1) / kThreads);
+  k_set_weights<<<grid, kThreads, 0, stream>>>(s, w, fixed);
   return hipGetLastError();
 }
 
@@ -6215,10 +6264,15 @@ hipError_t launch_gnc_snapshot(int r, int b, const GncEntries& g, const double* 
 }
 
 hipError_t launch_gnc_weights(int r, int b, const GncEntries& g, const double* X, const double* RX,
-                              const RobustParams& rp, double* w_prob, double* w_g, hipStream_t stream) {
+                              const RobustParams& rp, double* w_prob, double* w_g, const unsigned char* fixed,
+                              hipStream_t stream) {
   if (g.n == 0) return hipSuccess;
   const int grid = (g.n + kThreads - 1) / kThreads;
-  DPGO_DISPATCH(r, b, (k_gnc_weights<R, B - 1><<<grid, kThreads, 0, stream>>>(g, X, RX, rp, w_prob, w_g)));
+  if (fixed) {
+    DPGO_DISPATCH(r, b, (k_gnc_weights<R, B - 1, true><<<grid, kThreads, 0, stream>>>(g, X, RX, rp, w_prob, w_g, fixed)));
+  } else {
+    DPGO_DISPATCH(r, b, (k_gnc_weights<R, B - 1, false><<<grid, kThreads, 0, stream>>>(g, X, RX, rp, w_prob, w_g, nullptr)));
+  }
   return hipGetLastError();
 }
 

@@ -144,7 +144,29 @@ struct dpgo_rbcd_s {
     long prob_edges = 0;  // length of the colour's w_prob
   };
   std::vector<WMap> wmap;
-  std::vector<int> odo_edges;  // graph edges that are odometry of an owned agent: weight 1, never reweighted
+  std::vector<int> odo_edges;  // graph edges that are odometry of an owned agent: never reweighted (1 until set)
+  // weights from outside (dpgo_rbcd_set_weights): per colour the graph edge of every destination k_set_weights
+  // writes -- the colour problem's edges, its G entries, its GNC entries, in that order -- kept on the host at
+  // creation and uploaded by the first call, with the flag arrays the flagged kernels read (one per GNC entry, one
+  // per problem edge).  odo_color / odo_prob_edge: where an odometry edge's weight sits, for dpgo_rbcd_get_weights.
+  struct WSet {
+    std::vector<int> src;  // n_prob + n_g + n_gnc
+    int n_prob = 0, n_g = 0, n_gnc = 0;
+    DevBuf<int> src_dev;
+    DevBuf<unsigned char> fix_gnc, fix_prob;
+  };
+  std::vector<WSet> wset;
+  std::vector<int> odo_color, odo_prob_edge;
+  long n_edges = 0;              // edges of the creating graph: the length of the caller's w / fixed
+  bool wset_on_device = false;   // the tables are uploaded
+  bool weights_set = false;      // some dpgo_rbcd_set_weights* call has run
+  bool unit_q_kept = false;      // L2: the colour problems hold their unit-weight Q for dpgo_rbcd_central_eval
+  bool fixed_on = false;         // the last call gave flags: the reweighting kernels read them
+  DevBuf<double> w_stage;        // the host form's staging copy of w, then of fixed
+  DevBuf<unsigned char> fixed_stage;
+  // the staging copies are what the colour problems hold: set by the host form, cleared by the device form and by
+  // every reweighting (dpgo_rbcd_bench_set_weights may then repeat the gather without changing the engine)
+  bool stage_last = false;
   // edge errors (dpgo_rbcd_get_errors): the measurements dpgo_rbcd_get_weights reports for this rank (wmap's and
   // odo_edges, in the order creation meets them) as graph edge, the two pose sources in GncEntries' sign encoding
   // (>= 0 the owned buffer, -1 - slot the received poses) and R, t, kappa, tau.  Creation keeps the three ints per
@@ -253,6 +275,18 @@ int assemble_G(dpgo_rbcd e, int c, const double* Rx, bool unit_weights = false) 
   return DPGO_HIP_OK;
 }
 
+// computeConvergedLoopClosureRatio (:1247-1289) of colour c's agents at the colour's current weights (GNC_TLS only);
+// known inliers are left out once flags were given
+int converged_ratio(dpgo_rbcd e, int c) {
+  dpgo_hip_problem h = e->prob[c];
+  if (!h || e->P.robust_cost != DPGO_ROBUST_GNC_TLS) return DPGO_HIP_OK;
+  auto* l = e->lc[c];
+  HIP_TRY(launch_conv_ratio(h->K, l->off.p, l->idx.p, e->gnc[c]->w_prob.p, l->ratio.p,
+                            e->fixed_on ? e->wset[c].fix_prob.p : nullptr, e->stream));
+  l->valid = true;
+  return DPGO_HIP_OK;
+}
+
 // GNC / robust reweighting of colour c's loop closures at the current poses (own X buffer and the
 // received neighbour poses), then the on-device rebuild of the colour problem's Q.
 int reweight_color(dpgo_rbcd e, int c) {
@@ -262,13 +296,27 @@ int reweight_color(dpgo_rbcd e, int c) {
   const GncEntries ge{g->n, g->prob_edge.p, g->g_entry.p, g->src1.p, g->src2.p, g->R.p, g->t.p, g->kappa.p,
                       g->tau.p, g->agent.p, g->nbr_end.p, g->dict.p, g->dict_ok.p};
   const RobustParams rp{e->P.robust_cost, e->mu, e->P.gnc_barc, e->P.huber_threshold, e->P.tls_threshold};
-  HIP_TRY(launch_gnc_weights(e->r, e->b, ge, e->X.p, e->RX.p, rp, g->w_prob.p, e->gt[c]->w.p, e->stream));
+  e->stage_last = false;  // the weights move away from what was staged
+  // known inliers (dpgo_rbcd_set_weights' flags): null unless the last call gave some
+  HIP_TRY(launch_gnc_weights(e->r, e->b, ge, e->X.p, e->RX.p, rp, g->w_prob.p, e->gt[c]->w.p,
+                             e->fixed_on ? e->wset[c].fix_gnc.p : nullptr, e->stream));
   DPGO_TRY(dpgo_hip_set_edge_weights_dev(h, g->w_prob.p));
-  if (e->P.robust_cost == DPGO_ROBUST_GNC_TLS) {  // computeConvergedLoopClosureRatio (:1247-1289)
-    auto* l = e->lc[c];
-    HIP_TRY(launch_conv_ratio(h->K, l->off.p, l->idx.p, g->w_prob.p, l->ratio.p, e->stream));
-    l->valid = true;
+  DPGO_TRY(converged_ratio(e, c));
+  return DPGO_HIP_OK;
+}
+
+// XPrev = V = Y = X, gamma = alpha = 0: PGOAgent::initializeAcceleration (:1062-1071), which the reference runs
+// after every reweighting (:655-660); a dpgo_rbcd_set_weights* call changes the problem in the same way
+int initialize_acceleration(dpgo_rbcd e) {
+  const long bytes = static_cast<long>(sizeof(double)) * e->Nown * static_cast<long>(e->rb());
+  if (bytes) {
+    HIP_TRY(hipMemcpyAsync(e->Xprev.p, e->X.p, bytes, hipMemcpyDeviceToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(e->V.p, e->X.p, bytes, hipMemcpyDeviceToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(e->Y.p, e->X.p, bytes, hipMemcpyDeviceToDevice, e->stream));
   }
+  e->gamma = 0.0;
+  e->alpha = 0.0;
+  std::fill(e->v_pending.begin(), e->v_pending.end(), 0);  // V = X supersedes a deferred updateV
   return DPGO_HIP_OK;
 }
 
@@ -611,7 +659,10 @@ int dpgo_rbcd_create(dpgo_graph g, int num_agents, const int* agent_of_pose, con
   e->lc.assign(e->ncolors, nullptr);
   e->asz.assign(e->ncolors, {});
   e->g_store_calls.assign(e->ncolors, 0);
+  e->wset.resize(e->ncolors);
+  e->n_edges = static_cast<long>(m);
   for (int c = 0; c < e->ncolors; ++c) {
+    std::vector<int> ws_prob, ws_g;  // graph edge per problem edge / per G entry (dpgo_rbcd_set_weights)
     e->gt[c] = new dpgo_rbcd_s::GTab();
     e->gnc[c] = new dpgo_rbcd_s::Gnc();
     e->lc[c] = new dpgo_rbcd_s::LcList();
@@ -649,6 +700,7 @@ int dpgo_rbcd_create(dpgo_graph g, int num_agents, const int* agent_of_pose, con
         et.insert(et.end(), &g->t[k * d], &g->t[k * d] + d);
         ek.push_back(g->kappa[k]);
         etau.push_back(g->tau[k]);
+        ws_prob.push_back(static_cast<int>(k));
         if (!(own_i && own_j)) slots[own_i ? local[i] : local[j]].push_back(k);
       }
       if (e->P.q_format == DPGO_QFMT_BSR) {  // explicit Q_A (BSR), as the reference materialises it
@@ -692,6 +744,7 @@ int dpgo_rbcd_create(dpgo_graph g, int num_agents, const int* agent_of_pose, con
           kv.push_back(g->kappa[k]);
           tauv.push_back(g->tau[k]);
           wv.push_back(1.0);
+          ws_g.push_back(static_cast<int>(k));
         }
         slot_off.push_back(static_cast<int>(src.size()));
       }
@@ -717,6 +770,8 @@ int dpgo_rbcd_create(dpgo_graph g, int num_agents, const int* agent_of_pose, con
         if (own_i && own_j) {
           if (local[j] == local[i] + 1) {  // odometry: never reweighted
             e->odo_edges.push_back(static_cast<int>(k));
+            e->odo_color.push_back(c);
+            e->odo_prob_edge.push_back(static_cast<int>(prob_edges + static_cast<long>(x)));
             err_entry(k, static_cast<int>(owned_index(i)), static_cast<int>(owned_index(j)));
             continue;
           }
@@ -774,6 +829,16 @@ int dpgo_rbcd_create(dpgo_graph g, int num_agents, const int* agent_of_pose, con
     auto* gc = e->gnc[c];
     e->wmap[c].prob_edges = prob_edges;
     gc->n = static_cast<int>(gn_pe.size());
+    {
+      // the GNC entries are met in wmap's order, so its graph edges are their sources
+      auto& S = e->wset[c];
+      S.n_prob = static_cast<int>(ws_prob.size());
+      S.n_g = static_cast<int>(ws_g.size());
+      S.n_gnc = gc->n;
+      S.src = std::move(ws_prob);
+      S.src.insert(S.src.end(), ws_g.begin(), ws_g.end());
+      S.src.insert(S.src.end(), e->wmap[c].graph_edge.begin(), e->wmap[c].graph_edge.end());
+    }
     if (rc == DPGO_HIP_OK) rc = upload_vec(gc->prob_edge, gn_pe, e->stream);
     if (rc == DPGO_HIP_OK) rc = upload_vec(gc->g_entry, gn_ge, e->stream);
     if (rc == DPGO_HIP_OK) rc = upload_vec(gc->src1, gn_s1, e->stream);
@@ -792,7 +857,7 @@ int dpgo_rbcd_create(dpgo_graph g, int num_agents, const int* agent_of_pose, con
     // weights it is 1, and 0/0 = NaN for an agent without loop closures (which is then ready whatever the threshold)
     if (rc == DPGO_HIP_OK && e->P.robust_cost == DPGO_ROBUST_GNC_TLS) {
       auto* l = e->lc[c];
-      if (launch_conv_ratio(h->K, l->off.p, l->idx.p, gc->w_prob.p, l->ratio.p, e->stream) != hipSuccess)
+      if (launch_conv_ratio(h->K, l->off.p, l->idx.p, gc->w_prob.p, l->ratio.p, nullptr, e->stream) != hipSuccess)
         rc = fail(DPGO_HIP_EDEVICE, "converged ratio");
       l->valid = true;
     }
@@ -1197,12 +1262,14 @@ int dpgo_rbcd_get_errors(dpgo_rbcd e, const double* recv_dev, int rounded, const
 
 int dpgo_rbcd_get_weights(dpgo_rbcd e, double* w) {
   if (!e || !w) return fail(DPGO_HIP_EINVAL, "null argument");
-  for (int k : e->odo_edges) w[k] = 1.0;
-  const bool l2 = e->P.robust_cost == DPGO_ROBUST_L2;  // never reweighted: no device read
+  // never reweighted and never set: every weight is 1, no device read
+  const bool l2 = e->P.robust_cost == DPGO_ROBUST_L2 && !e->weights_set;
+  if (!e->weights_set)
+    for (int k : e->odo_edges) w[k] = 1.0;
   std::vector<double> host;
   for (int c = 0; c < e->ncolors; ++c) {
     const auto& M = e->wmap[c];
-    if (M.graph_edge.empty()) continue;
+    if (!e->prob[c] || M.prob_edges == 0 || (M.graph_edge.empty() && !e->weights_set)) continue;
     if (!l2) {
       host.resize(static_cast<size_t>(M.prob_edges));
       HIP_TRY(hipMemcpyAsync(host.data(), e->gnc[c]->w_prob.p, sizeof(double) * host.size(), hipMemcpyDeviceToHost,
@@ -1210,7 +1277,112 @@ int dpgo_rbcd_get_weights(dpgo_rbcd e, double* w) {
       HIP_TRY(hipStreamSynchronize(e->stream));
     }
     for (size_t x = 0; x < M.graph_edge.size(); ++x) w[M.graph_edge[x]] = l2 ? 1.0 : host[M.prob_edge[x]];
+    if (e->weights_set)  // odometry reports what was set
+      for (size_t x = 0; x < e->odo_edges.size(); ++x)
+        if (e->odo_color[x] == c) w[e->odo_edges[x]] = host[e->odo_prob_edge[x]];
   }
+  return DPGO_HIP_OK;
+}
+
+// The body of both dpgo_rbcd_set_weights forms: w_dev / fixed_dev are device arrays in the graph's edge order.
+static int set_weights_body(dpgo_rbcd e, const double* w_dev, const unsigned char* fixed_dev) {
+  DPGO_TRY(join_side(e));
+  if (!e->unit_q_kept && e->P.robust_cost == DPGO_ROBUST_L2) {  // the unit-weight Q of dpgo_rbcd_central_eval
+    for (auto* h : e->prob)
+      if (h) DPGO_TRY(keep_unit_q(h));
+    e->unit_q_kept = true;  // before Q changes, and never again: a retried call must not keep a reweighted Q
+  }
+  if (!e->wset_on_device) {
+    for (int c = 0; c < e->ncolors; ++c)
+      if (e->prob[c]) DPGO_TRY(upload_vec(e->wset[c].src_dev, e->wset[c].src, e->stream));
+    e->wset_on_device = true;
+  }
+  // every flag buffer exists before any state changes: whatever fails below, a later reweighting reads allocated
+  // memory, and the flags it honours are the previous call's until this one has gone through
+  if (fixed_dev)
+    for (int c = 0; c < e->ncolors; ++c) {
+      if (!e->prob[c]) continue;
+      HIP_TRY(e->wset[c].fix_gnc.ensure(std::max(e->wset[c].n_gnc, 1)));
+      HIP_TRY(e->wset[c].fix_prob.ensure(std::max(e->wset[c].n_prob, 1)));
+    }
+  const bool fixed_before = e->fixed_on;
+  e->fixed_on = fixed_dev != nullptr;  // converged_ratio below reads it
+  auto per_color = [&]() -> int {
+    for (int c = 0; c < e->ncolors; ++c) {
+      dpgo_hip_problem h = e->prob[c];
+      if (!h) continue;
+      auto& S = e->wset[c];
+      const SetWeights sw{S.n_prob, S.n_g, S.n_gnc, S.src_dev.p, e->gnc[c]->w_prob.p, e->gt[c]->w.p, S.fix_gnc.p,
+                          S.fix_prob.p};
+      HIP_TRY(launch_set_weights(sw, w_dev, fixed_dev, e->stream));
+      DPGO_TRY(dpgo_hip_set_edge_weights_dev(h, e->gnc[c]->w_prob.p));  // Q, block-Jacobi, the exact factor follows
+      DPGO_TRY(converged_ratio(e, c));
+    }
+    return DPGO_HIP_OK;
+  };
+  const int rc = per_color();
+  if (rc != DPGO_HIP_OK) {
+    e->fixed_on = fixed_before;
+    return rc;
+  }
+  e->weights_set = true;
+  e->next_y.valid = false;  // what was written ahead belongs to the old problem
+  if (e->P.acceleration) DPGO_TRY(initialize_acceleration(e));
+  return DPGO_HIP_OK;
+}
+
+static int check_set_weights(dpgo_rbcd e, const double* w) {
+  if (!e || !w) return fail(DPGO_HIP_EINVAL, "null argument");
+  if (e->P.q_format != DPGO_QFMT_EDGES)
+    return fail(DPGO_HIP_EINVAL, "set_weights reweights an edge-stream Q (q_format DPGO_QFMT_EDGES)");
+  return DPGO_HIP_OK;
+}
+
+int dpgo_rbcd_set_weights(dpgo_rbcd e, const double* w, const unsigned char* fixed) {
+  DPGO_TRY(check_set_weights(e, w));
+  const size_t m = static_cast<size_t>(e->n_edges);
+  for (size_t k = 0; k < m; ++k)
+    if (!(w[k] >= 0.0) || !std::isfinite(w[k]))
+      return fail(DPGO_HIP_EINVAL, "set_weights: weight of edge " + std::to_string(k) + " is negative or not finite");
+  HIP_TRY(e->w_stage.ensure(std::max<size_t>(m, 1)));
+  if (fixed) HIP_TRY(e->fixed_stage.ensure(std::max<size_t>(m, 1)));
+  if (m) HIP_TRY(hipMemcpyAsync(e->w_stage.p, w, sizeof(double) * m, hipMemcpyHostToDevice, e->stream));
+  if (m && fixed) HIP_TRY(hipMemcpyAsync(e->fixed_stage.p, fixed, m, hipMemcpyHostToDevice, e->stream));
+  DPGO_TRY(set_weights_body(e, e->w_stage.p, fixed ? e->fixed_stage.p : nullptr));
+  HIP_TRY(hipStreamSynchronize(e->stream));  // the caller's arrays are free again
+  e->stage_last = true;
+  return DPGO_HIP_OK;
+}
+
+int dpgo_rbcd_set_weights_dev(dpgo_rbcd e, const double* w_dev, const unsigned char* fixed_dev) {
+  DPGO_TRY(check_set_weights(e, w_dev));
+  e->stage_last = false;
+  return set_weights_body(e, w_dev, fixed_dev);
+}
+
+int dpgo_rbcd_bench_set_weights(dpgo_rbcd e, int color, int reps, double* ms) {
+  if (!e || color < 0 || color >= e->ncolors || reps <= 0 || !ms) return fail(DPGO_HIP_EINVAL, "bad arguments");
+  if (!e->stage_last)
+    return fail(DPGO_HIP_ESTATE, "bench_set_weights repeats the launch of a host-form dpgo_rbcd_set_weights with no "
+                                 "reweighting since");
+  *ms = 0.0;
+  if (!e->prob[color]) return DPGO_HIP_OK;
+  DPGO_TRY(join_side(e));
+  auto& S = e->wset[color];
+  const SetWeights sw{S.n_prob, S.n_g, S.n_gnc, S.src_dev.p, e->gnc[color]->w_prob.p, e->gt[color]->w.p, S.fix_gnc.p,
+                      S.fix_prob.p};
+  const unsigned char* fx = e->fixed_on ? e->fixed_stage.p : nullptr;
+  ScopedEvents sev(2);
+  HIP_TRY(sev.create());
+  for (int i = 0; i < kBenchWarmup + reps; ++i) {  // the same values again: the engine's state does not change
+    if (i == kBenchWarmup) HIP_TRY(hipEventRecord(sev.ev[0], e->stream));
+    HIP_TRY(launch_set_weights(sw, e->w_stage.p, fx, e->stream));
+  }
+  HIP_TRY(hipEventRecord(sev.ev[1], e->stream));
+  HIP_TRY(hipEventSynchronize(sev.ev[1]));
+  float t = 0.f;
+  HIP_TRY(hipEventElapsedTime(&t, sev.ev[0], sev.ev[1]));
+  *ms = static_cast<double>(t) / reps;
   return DPGO_HIP_OK;
 }
 
@@ -1255,17 +1427,7 @@ int dpgo_rbcd_pre_exchange(dpgo_rbcd e, int color) {
   if (e->gnc_due) {
     for (int c = 0; c < e->ncolors; ++c)
       if (c != color) DPGO_TRY(reweight_color(e, c));
-    if (e->P.acceleration) {  // initializeAcceleration (:1062-1071): XPrev = V = Y = X, gamma = alpha = 0
-      const long bytes = static_cast<long>(sizeof(double)) * e->Nown * static_cast<long>(e->rb());
-      if (bytes) {
-        HIP_TRY(hipMemcpyAsync(e->Xprev.p, e->X.p, bytes, hipMemcpyDeviceToDevice, e->stream));
-        HIP_TRY(hipMemcpyAsync(e->V.p, e->X.p, bytes, hipMemcpyDeviceToDevice, e->stream));
-        HIP_TRY(hipMemcpyAsync(e->Y.p, e->X.p, bytes, hipMemcpyDeviceToDevice, e->stream));
-      }
-      e->gamma = 0.0;
-      e->alpha = 0.0;
-      std::fill(e->v_pending.begin(), e->v_pending.end(), 0);  // V = X supersedes a deferred updateV
-    }
+    if (e->P.acceleration) DPGO_TRY(initialize_acceleration(e));
   }
   const bool restart = restart_now(e);
   // XPrev = X (:673): every agent's on a restart iteration (restartNesterovAcceleration reads it);
@@ -1473,6 +1635,10 @@ static int update_body(dpgo_rbcd e, int color, dpgo_opt_result* results) {
 }
 
 int dpgo_rbcd_central_eval(dpgo_rbcd e, const double* recv_dev, double* f_out, double* gradnorm_sq) {
+  return dpgo_rbcd_central_eval_ex(e, recv_dev, 0, f_out, gradnorm_sq);
+}
+
+int dpgo_rbcd_central_eval_ex(dpgo_rbcd e, const double* recv_dev, int weighted, double* f_out, double* gradnorm_sq) {
   if (e) DPGO_TRY(join_side(e));
   if (!e) return fail(DPGO_HIP_EINVAL, "null engine");
   if (e->n_recv_poses > 0) {
@@ -1482,8 +1648,10 @@ int dpgo_rbcd_central_eval(dpgo_rbcd e, const double* recv_dev, double* f_out, d
   }
   // per colour: G from the current neighbour poses, then f / |P_X(XQ + G)|^2 / <G, X> per agent.  The example's
   // central evaluation uses the dataset's Q (QCentral, unit weights): under a robust cost the reweighted colour
-  // problems evaluate on their unit-weight copy of Q and G is assembled with unit weights.
-  const bool unit = e->P.robust_cost != DPGO_ROBUST_L2;
+  // problems evaluate on their unit-weight copy of Q and G is assembled with unit weights; likewise once weights were
+  // set from outside.  weighted != 0 instead evaluates the problem being solved: the colour problems' current Q, G
+  // with the entries' current weights.
+  const bool unit = !weighted && (e->P.robust_cost != DPGO_ROBUST_L2 || e->weights_set);
   for (int c = 0; c < e->ncolors; ++c) {
     if (!e->prob[c]) continue;
     DPGO_TRY(assemble_G(e, c, e->RXc.p, unit));

@@ -1229,6 +1229,10 @@ _SIGS2 = [
     ("dpgo_rbcd_bench_hvp", [C.c_void_p, C.c_int, C.c_int, _dp], C.c_int),
     ("dpgo_rbcd_reset_stream", [C.c_void_p], C.c_int),
     ("dpgo_rbcd_central_eval", [C.c_void_p, C.c_void_p, _dp, _dp], C.c_int),
+    ("dpgo_rbcd_central_eval_ex", [C.c_void_p, C.c_void_p, C.c_int, _dp, _dp], C.c_int),
+    ("dpgo_rbcd_set_weights", [C.c_void_p, _dp, C.c_void_p], C.c_int),
+    ("dpgo_rbcd_set_weights_dev", [C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    ("dpgo_rbcd_bench_set_weights", [C.c_void_p, C.c_int, C.c_int, _dp], C.c_int),
     ("dpgo_rbcd_status", [C.c_void_p, _dp, _ip], C.c_int),
     ("dpgo_rbcd_stats", [C.c_void_p, _ip], C.c_int),
     ("dpgo_rbcd_bytes", [C.c_void_p, _dp, _dp], C.c_int),
@@ -1808,6 +1812,13 @@ def weight_owner(graph: "Graph", agent_of_pose, num_agents):
     return out
 
 
+def pcm_weights(edge_inlier):
+    """Graph.pcm's edge_inlier as Rbcd.set_weights' (w, fixed): a rejected closure (0) is held at weight 0, an accepted
+    one (1) and an edge PCM does not judge (255: odometry, private closures) start at 1 and stay free."""
+    rejected = np.asarray(edge_inlier) == 0
+    return np.where(rejected, 0.0, 1.0), rejected.astype(np.uint8)
+
+
 def lifting_matrix(d, r, seed=2):
     """Repo-defined lifting matrix YLift in St(d, r) (replaces ROPTLIB's RNG)."""
     M = np.random.default_rng(seed).standard_normal((r, d))
@@ -2047,12 +2058,40 @@ class Rbcd:
     def reset_stream(self):
         _check(lib().dpgo_rbcd_reset_stream(self.h))
 
-    def central_eval(self, recv_ptr=None):
-        """(this rank's central cost share, |RieGrad|^2 per agent [num_agents]) at the current X."""
+    def central_eval(self, recv_ptr=None, weighted=False):
+        """(this rank's central cost share, |RieGrad|^2 per agent [num_agents]) at the current X: at unit weights, or
+        with weighted=True of the problem the engine is solving (the weights last set or left by the reweighting)."""
         f = C.c_double()
         g = np.zeros(self.num_agents)
-        _check(lib().dpgo_rbcd_central_eval(self.h, C.c_void_p(recv_ptr or 0), C.byref(f), g.ctypes.data_as(_dp)))
+        _check(lib().dpgo_rbcd_central_eval_ex(self.h, C.c_void_p(recv_ptr or 0), 1 if weighted else 0, C.byref(f),
+                                               g.ctypes.data_as(_dp)))
         return f.value, g
+
+    def set_weights(self, w, fixed=None):
+        """Measurement weights from outside (dpgo_rbcd_set_weights): w one weight per edge in the graph's order,
+        finite and >= 0; fixed (optional, one flag per edge) marks known inliers that GNC never rewrites and the
+        converged ratio leaves out.  Replaces earlier weights and flags; an invalid weight or a BSR-format engine
+        raises and changes nothing."""
+        wv, wp = _f64(w)
+        if wv.size != self.graph.m:
+            raise ValueError(f"w has {wv.size} entries, the graph has {self.graph.m} edges")
+        fv = None
+        if fixed is not None:
+            fv = np.ascontiguousarray(np.asarray(fixed) != 0, dtype=np.uint8)
+            if fv.size != self.graph.m:
+                raise ValueError(f"fixed has {fv.size} entries, the graph has {self.graph.m} edges")
+        _check(lib().dpgo_rbcd_set_weights(self.h, wp, C.c_void_p(fv.ctypes.data if fv is not None else 0)))
+
+    def set_weights_dev(self, w_ptr, fixed_ptr=0):
+        """The same from device pointers (m doubles, m bytes or 0) valid until the engine's stream has passed the
+        call; the caller guarantees finite weights >= 0."""
+        _check(lib().dpgo_rbcd_set_weights_dev(self.h, C.c_void_p(w_ptr), C.c_void_p(fixed_ptr or 0)))
+
+    def bench_set_weights(self, color, reps=1):
+        """ms per k_set_weights launch of one colour, repeating the host-form set_weights call just made."""
+        ms = C.c_double()
+        _check(lib().dpgo_rbcd_bench_set_weights(self.h, int(color), int(reps), C.byref(ms)))
+        return ms.value
 
     def status(self):
         """(relativeChange[num_agents], readyToTerminate[num_agents]); NaN / -1 for other ranks' agents."""

@@ -373,9 +373,32 @@ int dpgo_rbcd_gram(dpgo_rbcd e, double* C);
 int dpgo_rbcd_get_X_reduced(dpgo_rbcd e, int k, const double* W, double* Xk_global);
 /* current weight of every measurement this rank is responsible for, at its index in the graph's
  * edge order (w[m]; entries of other ranks' edges untouched).  Responsible = dpgo_rbcd_weight_owner's agent
- * lives on this rank; odometry (owner -1) is written by the rank of its agent, always 1.  With
- * robust_cost L2 every written entry is exactly 1. */
+ * lives on this rank; odometry (owner -1) is written by the rank of its agent: 1 until dpgo_rbcd_set_weights, then
+ * the value that was set.  With robust_cost L2 and no weights set every written entry is exactly 1 (nothing is read
+ * from the device). */
 int dpgo_rbcd_get_weights(dpgo_rbcd e, double* w);
+/* Weights and known inliers from outside (the reference's RelativeSEMeasurement::weight and ::isKnownInlier,
+ * src/PGOAgent.cpp:742-744, 796-798, 1186, 1203, 1257, 1266).  w[m]: one weight per edge of the graph the engine
+ * was created from, in its edge order -- the full array on every rank (as dpgo_rbcd_set_X's X_global); a rank uses
+ * the entries of the copies it holds, nothing is communicated.  fixed[m] (may be NULL = no edge fixed): nonzero
+ * marks a known inlier, which no reweighting rewrites and the converged ratio leaves out of count and total.  A call
+ * replaces both the weights and the flags.  Odometry weights are set like any other and never reweighted; their flag
+ * is ignored.  Both agents' copies of a shared edge take the weight and the flag; afterwards GNC rewrites the
+ * responsible (lower-ID) copy only, the other keeps what was set.  On the engine's stream: the colour problems' Q,
+ * block-Jacobi inverses and (lazily) exact factors follow, the converged ratios are recomputed (GNC_TLS), and with
+ * acceleration PGOAgent::initializeAcceleration runs (XPrev = V = Y = X, gamma = alpha = 0) as after a reweighting.
+ * mu, the GNC iteration count and the iteration number are untouched.
+ * The host form validates first: a negative or non-finite weight, or an engine whose q_format is not
+ * DPGO_QFMT_EDGES, is DPGO_HIP_EINVAL and leaves the engine unchanged; it synchronises.  The _dev form takes device
+ * pointers (w 8-byte aligned) valid until the stream has passed the call; its caller guarantees finite weights
+ * >= 0 (only q_format is checked). */
+int dpgo_rbcd_set_weights(dpgo_rbcd e, const double* w, const unsigned char* fixed);
+int dpgo_rbcd_set_weights_dev(dpgo_rbcd e, const double* w_dev, const unsigned char* fixed_dev);
+/* Average ms (HIP events on the engine's stream) of `reps` launches of k_set_weights for colour class c, repeating
+ * the launch of the last host-form dpgo_rbcd_set_weights (the same values, so the engine does not change).  After a
+ * device-form call or any reweighting since that call the staged values are no longer the engine's:
+ * DPGO_HIP_ESTATE, nothing launched. */
+int dpgo_rbcd_bench_set_weights(dpgo_rbcd e, int color, int reps, double* ms);
 /* The residuals behind those weights: err = kappa |Y1 R - Y2|_F^2 + tau |p2 - p1 - Y1 t|^2 (and its two parts) of
  * exactly the measurements dpgo_rbcd_get_weights reports for this rank, at the engine's current X after whatever is
  * queued on its stream, written at their index in the graph's edge order (err, rot_sq, tra_sq of m doubles, each
@@ -455,6 +478,13 @@ int dpgo_rbcd_tcg_blocks(dpgo_rbcd e, int color, int* blocks_last, int* agent_ti
  * last update (required when world > 1).  gradnorm_sq[num_agents]: 0 for agents of other ranks.
  * Synchronises. */
 int dpgo_rbcd_central_eval(dpgo_rbcd e, const double* recv_dev, double* f_out, double* gradnorm_sq);
+/* weighted = 0: dpgo_rbcd_central_eval (unit weights, always -- also after dpgo_rbcd_set_weights).  weighted = 1: the
+ * problem the engine is solving -- the colour problems' current Q (the weights last set or last left by the
+ * reweighting) and G assembled with the entries' current weights: this rank's share of 1/2 <X Q_w, X> and the
+ * per-agent |RieGrad|^2 of that problem.  A shared edge's two copies enter with their own weights (equal after a
+ * set_weights, until GNC rewrites the responsible one). */
+int dpgo_rbcd_central_eval_ex(dpgo_rbcd e, const double* recv_dev, int weighted, double* f_out,
+                              double* gradnorm_sq);
 /* PGOAgentStatus of every owned agent's last selected update (src/PGOAgent.cpp:700-716):
  * relativeChange and readyToTerminate, written at the agent's global index (others untouched).
  * PGOAgent::shouldTerminate (:1007-1031) = every agent ready, gathered over ranks by the caller. */
